@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- 1080p frame-pairs/s at DIS operating point 2 (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = one pass of the whole hot path (pyramid+gradients -> per-scale LK -> densify -> variational refinement)
@@ -12,10 +12,20 @@ data-path collective); value = pairs all ranks processed / max-over-ranks time.
 Batches in flight: the path is latency-bound at batch 64 (the refinement keeps a quarter of the CUs busy), so consecutive
 steps -- each a complete batch -- are submitted to --in-flight engine contexts on internal streams in turn
 (flowonthego_amd.FlowPipeline = fotg_pipe_* of include/fotg.h) and overlap on the GPU; every window still holds exactly K
-complete steps between its barriers (the window ends with a host wait for all contexts).  The same window with one batch at
-a time through a single context (fotg_calc_batch) is timed too and reported as `one_batch_at_a_time`.
+complete steps between its barriers (the window ends with a host wait for all contexts).
 
-Extra objects in the JSON line:
+A plain run sets up, warms up (W steps), times ONE window of exactly K steps, writes the last step's flows if --dump-outputs
+is given, and prints the result line: `value`, `ms_per_step` (= window / K) and the contract's keys, nothing else.
+--dump-outputs DIR: the finest-scale flows of the batch the last timed step computed (what fotg_calc_batch / fotg_pipe_submit
+hand back), float32, as DIR/flow.npy (rank r > 0: DIR/flow_rank<r>.npy); the inputs are seeded, so the same arguments give
+the same inputs in every run.
+
+--full adds everything else and keeps the side file of the detail (bench_detail.json) and its copy on stderr: the K-step window
+repeated --windows times (default 25, the median reported), a check that every pipeline slot gives the bits of one context, the
+same window with one batch at a time through a single context (fotg_calc_batch, `one_batch_at_a_time`), the host's issue time
+per step, and, on rank 0, the legs below.
+
+Extra objects in the JSON line (--full):
   roofline      HBM roofline of the kernel that moves the path's algorithmic bytes (pyr_base_kernel: every input byte
                 exactly once), duration measured live with HIP events on the launch stream
   rooflines     the same for the three kernels that hold most of a step's time (pyr_base, the fused refinement level, one
@@ -612,7 +622,8 @@ def short_line(res):
                    "global_batch": cfg.get("global_batch"), "pairs_in_flight": cfg.get("pairs_in_flight"),
                    "batches_in_flight_per_gpu": res.get("batches_in_flight"),
                    "parallelism": "frame-pair sharding x%s, no collective" % res.get("n_gpus")}
-    s["one_batch_at_a_time"] = _pick(res.get("one_batch_at_a_time", {}), ("value", "ms_per_step"), 6)
+    if "one_batch_at_a_time" in res:
+        s["one_batch_at_a_time"] = _pick(res["one_batch_at_a_time"], ("value", "ms_per_step"), 6)
     if "roofline" in res:
         s["roofline"] = _pick(res["roofline"], ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch",
                                                 "ms_per_launch", "ms_per_launch_back_to_back", "unavailable"), 5)
@@ -673,9 +684,15 @@ def short_line(res):
     return s
 
 
-def emit(res):
+def emit(res, detail=True):
     """detail -> bench_detail.json (gpurun_out/ when it can be created, else the working directory) and stderr; the short line ->
     stdout, last"""
+    if not detail:                           # a plain run: the line alone, no side file
+        s = short_line(res)
+        s.pop("detail", None)
+        sys.stdout.flush()
+        print(json.dumps(s, separators=(",", ":")), flush=True)
+        return
     detail = json.dumps(res)
     for d in (os.path.join(ROOT, "gpurun_out"), os.getcwd()):
         try:
@@ -696,6 +713,21 @@ def emit(res):
         line = json.dumps(s, separators=(",", ":"))
     sys.stdout.flush()
     print(line, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(d, flows, rank, world):
+    """--dump-outputs DIR: the finest-scale flows (batch, h, w, 2) the last timed step left in its output buffer, float32, as
+    DIR/flow.npy (rank r > 0: DIR/flow_rank<r>.npy).  A batch too large for this rank's share of DUMP_MAX_BYTES is cut to a fixed,
+    seeded sample of its pairs (sorted), the same in every run with the same arguments."""
+    f = flows.detach().float().cpu().numpy()
+    cap = max(1, (DUMP_MAX_BYTES // world) // max(1, f[0].nbytes))
+    if f.shape[0] > cap:
+        f = f[np.sort(np.random.default_rng(0).choice(f.shape[0], cap, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "flow.npy" if rank == 0 else "flow_rank%d.npy" % rank), np.ascontiguousarray(f, np.float32))
 
 
 def _free_port():
@@ -751,13 +783,17 @@ def main():
     ap.add_argument("--steps", type=int, default=100, help="steps per timed window (with batches in flight a window starts with an empty pipeline and ends with a drain: short windows under-report)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="frame pairs per GPU per step (BASELINE configs[2]: 64)")
-    ap.add_argument("--windows", type=int, default=25, help="repeats of the timed K-step window; the median window is reported")
+    ap.add_argument("--windows", type=int, default=None, help="repeats of the timed K-step window; the median window is reported "
+                    "(default: 1, with --full 25)")
     ap.add_argument("--in-flight", type=int, default=4, help="batches in flight per GPU: consecutive steps go to this many engine "
                     "contexts on internal streams in turn (flowonthego_amd.FlowPipeline / fotg_pipe_*); 1 = one batch at a time "
                     "through a single context (fotg_calc_batch), which is also timed and reported beside `value`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-breakdown", action="store_true")
-    ap.add_argument("--extras", action="store_true", help="also time the stereo depth mode")
+    ap.add_argument("--full", action="store_true", help="besides the headline: repeated windows, the pipe-vs-one-context check, "
+                    "one batch at a time, stage times, rooflines, the other modes and configs, the CPU baseline, the detail side file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the flows the last timed step computed to DIR/flow.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-breakdown", action="store_true", help="(--full) skip stage times, rooflines and the other legs")
+    ap.add_argument("--extras", action="store_true", help="(--full) also time the stereo depth mode")
     ap.add_argument("--scatter-gather", action="store_true", help="multi-rank runs: also time rank 0 scattering the frames of all "
                     "ranks over RCCL and gathering the flows back (SURVEY 8e); reported beside `value`, never part of it")
     ap.add_argument("--sor-mode", type=int, default=0, help="0 lexicographic (reference order, parity mode), 1 red-black")
@@ -767,6 +803,11 @@ def main():
 
     if a.gpus < 1:
         fail("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0 or (a.windows is not None and a.windows < 1):
+        fail("--steps and --windows must be >= 1, --warmup >= 0")
+    if a.extras and not a.full:
+        fail("--extras is a leg of --full")
+    windows = a.windows or (25 if a.full else 1)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under a launcher: become one (before anything touches the GPU) and relay the ranks' output and exit code
         sys.exit(self_launch(a.gpus, sys.argv[1:]))
@@ -866,28 +907,34 @@ def main():
             el = float(t.item())
         return el
 
-    run_steps(a.warmup, False)
+    if a.full or not pipe:
+        run_steps(a.warmup, False)
     if pipe:
         torch.cuda.synchronize()      # the pipe's streams do not wait for torch's: slot 0 shares its buffers with the warm-up above
         run_steps(max(a.warmup, D), True)
         torch.cuda.synchronize()
+    if pipe and a.full:
         same = all(torch.equal(ofc.calc_batch(f0, f1), o) for f0, f1, o in slots)           # pipelined results = single-context results, every slot
         if not same:
             print(json.dumps({"error": "a batch through the pipe differs from the same batch through one context", "rank": rank}))
             sys.exit(1)
-    # One window of K steps at this batch is ~10 ms -- too short to be robust against clock ramp and launch jitter.  The
-    # K-step window is therefore repeated (every repeat is again exactly K steps between barriers); `value` / `ms_per_step`
-    # are those of the MEDIAN window, the spread is reported beside them.
-    els = sorted(window(pipe is not None) for _ in range(max(1, a.windows)))
+    # One window of K steps at this batch is ~10 ms -- too short to be robust against clock ramp and launch jitter.  --full
+    # therefore repeats the K-step window (every repeat is again exactly K steps between barriers); `value` / `ms_per_step`
+    # are those of the MEDIAN window, the spread is reported beside them.  A plain run times one window.
+    els = sorted(window(pipe is not None) for _ in range(windows))
     el = els[len(els) // 2]
     ms_step = el / a.steps * 1e3
     value = world * a.batch * a.steps / el
-    els1 = sorted(window(False) for _ in range(max(1, min(a.windows, 9)))) if pipe else els
-    el1 = els1[len(els1) // 2]
+    if a.dump_outputs:
+        # the last step of every window is step K - 1, on slot (K - 1) % D; taken before anything else reuses the buffers
+        dump_outputs(a.dump_outputs, slots[(a.steps - 1) % D][2] if pipe else out, rank, world)
+    if a.full:
+        els1 = sorted(window(False) for _ in range(max(1, min(windows, 9)))) if pipe else els
+        el1 = els1[len(els1) // 2]
 
     # host side: time to ISSUE one step's launches (submit returns at once; nothing waits) -- shows whether the launch path limits
     # the in-flight rate (ms_per_step must stay above it)
-    if pipe:
+    if pipe and a.full:
         pipe.synchronize()
         t0 = time.perf_counter()
         for i in range(4 * D):
@@ -918,11 +965,12 @@ def main():
                                      "internal streams, fotg_pipe_*): step i runs on context i %% %d" % (D, D) if pipe else "")},
            "timed_windows": {"n": len(els), "steps_each": a.steps, "ms_per_step_median": ms_step, "ms_per_step_min": els[0] / a.steps * 1e3,
                              "ms_per_step_max": els[-1] / a.steps * 1e3},
-           "batches_in_flight": D,
-           "one_batch_at_a_time": {"value": world * a.batch * a.steps / el1, "unit": "frame-pairs/s", "ms_per_step": el1 / a.steps * 1e3,
-                                   "note": "the same K-step window with every step through ONE context on one stream (fotg_calc_batch), "
-                                           "each step starting when the previous one has finished on the GPU"}}
-    if pipe:
+           "batches_in_flight": D}
+    if a.full:
+        res["one_batch_at_a_time"] = {"value": world * a.batch * a.steps / el1, "unit": "frame-pairs/s", "ms_per_step": el1 / a.steps * 1e3,
+                                      "note": "the same K-step window with every step through ONE context on one stream (fotg_calc_batch), "
+                                              "each step starting when the previous one has finished on the GPU"}
+    if pipe and a.full:
         res["pipeline_matches_single_context"] = bool(same)
         res["pipeline_slots_compared"] = D
         res["host_issue_ms_per_step"] = host_issue_ms
@@ -935,7 +983,7 @@ def main():
         res["metric"] += " [SHARED-GPU TEST RUN: %d ranks on %d GPU(s), gloo]" % (world, ndev)
     res["rank_placement"] = placement
 
-    if rank == 0:
+    if rank == 0 and a.full:
         stream_ptr = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         if not a.no_breakdown:
             st = stage_breakdown(ofc, I0, I1, out, lib, stream_ptr)
@@ -1280,7 +1328,7 @@ def main():
         td.barrier()
         td.destroy_process_group()
     if rank == 0:
-        emit(res)                # the ONE stdout line, last
+        emit(res, detail=a.full)             # the ONE stdout line, last
 
 
 if __name__ == "__main__":

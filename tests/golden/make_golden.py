@@ -14,6 +14,8 @@ plain data and travel to the GPU box.
                         and halved four times; five inner iterations) -- the size class of the engine's streaming solver
                         (65..96 rows)
   fdf_ref_depth_*.npz   the same inputs through the reference's stereo-depth chain (RefLevelDE, :243-330)
+  fdf_ref_live.npz      inputs and outputs of every call the live-reference tests of tests/test_oracle.py make into oracle/_ref,
+                        recorded by running those tests (they replay it where oracle/_ref cannot be built)
   natural_images.npz    the reference's natural test images as 8-bit gray (same formula): images/road_HD.jpg (1920x1080) and
                         images/yosemite_4k.jpg (3840x2160) -- the inputs SURVEY.md 8(d) names for C2-C4 (the second frame of
                         a pair is a shifted copy, made by the test)
@@ -135,6 +137,21 @@ def depth_cases(noc):
     return out
 
 
+def live_ref_cases():
+    """run tests/test_oracle.py's live-reference tests against oracle/_ref and keep every call's inputs and outputs (RefCalls)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle as T
+    assert R.available(1) and R.available(3)
+    T.REF.stored = None                       # record afresh, do not pin against an older file
+    z = np.load(os.path.join(OUT, "alley_1_gray.npz"))
+    T.test_lk_half_with_live_reference_refinement({k: z[k] for k in z.files})
+    for c in T.VARREF_LIVE_CASES:
+        T.test_varref_vs_live_reference(*c)
+    for c in T.DEPTH_LIVE_CASES:
+        T.test_depth_varref_vs_live_reference(*c)
+    return T.REF.recorded
+
+
 def main():
     a0 = rgb(REF + "/images/alley_1/frame_0001.png")
     a1 = rgb(REF + "/images/alley_1/frame_0002.png")
@@ -148,6 +165,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "fdf_ref_l4_rgb.npz"), **fdf_level4_case(3))
     np.savez_compressed(os.path.join(OUT, "fdf_ref_depth_gray.npz"), **depth_cases(1))
     np.savez_compressed(os.path.join(OUT, "fdf_ref_depth_rgb.npz"), **depth_cases(3))
+    np.savez_compressed(os.path.join(OUT, "fdf_ref_live.npz"), **live_ref_cases())
     np.savez_compressed(os.path.join(OUT, "natural_images.npz"), road_HD=gray_cv(rgb(REF + "/images/road_HD.jpg")),
                         yosemite_4k=gray_cv(rgb(REF + "/images/yosemite_4k.jpg")))
     for f in sorted(os.listdir(OUT)):

@@ -273,7 +273,7 @@ def test_bench_gpus_2_end_to_end_on_one_gpu():
         pytest.skip("needs exactly one visible GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "FOTG_BENCH_ALLOW_SHARED_GPU")}
     args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "16", "--steps", "8", "--warmup", "2", "--windows", "3",
-            "--no-cpu-baseline", "--no-breakdown"]
+            "--full", "--no-cpu-baseline", "--no-breakdown"]
     r = subprocess.run(args, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and '"metric"' not in r.stdout
     r = subprocess.run(args, env=dict(env, FOTG_BENCH_ALLOW_SHARED_GPU="1"), capture_output=True, text=True, timeout=900)

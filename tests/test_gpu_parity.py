@@ -1144,7 +1144,7 @@ def test_bench_distributed_leg_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FOTG_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "16", "--steps", "8", "--warmup", "2", "--windows", "3",
-                        "--no-cpu-baseline", "--no-breakdown", "--scatter-gather"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-breakdown", "--scatter-gather"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) < 6000                      # ONE short line (the scatter / gather totals are scalars inside it)
@@ -1156,6 +1156,39 @@ def test_bench_distributed_leg_on_one_gpu():
     assert len(main["ms_per_step_per_rank"]) == 1 and main["pipeline_matches_single_context"]
     assert sg["gathered_shape"] == [16, 68, 120, 2] and sg["end_to_end_pairs_per_s"] > 0 and sg["gathered_flows_match_single_context"]
     assert main["rccl_ranks"] == 1 and main["rank_placement"][0]["pci_bus_id"]
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """a plain bench.py run (no --full) prints ONE line with the contract's keys and nothing of --full (no side file, no
+    one_batch_at_a_time), and --dump-outputs writes the flows of the last timed step: float32, the bits of the same seeded batch
+    through one context, and the same file in a second run"""
+    import importlib.util, json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    F, OFClass, _, _ = _mods()
+    K, D, B = 3, 4, 8
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", str(B), "--steps", str(K), "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == K and d["value"] > 0 and d["ms_per_step"] > 0 and d["value"] == pytest.approx(B / d["ms_per_step"] * 1e3, rel=1e-3)
+        assert "one_batch_at_a_time" not in d and "detail" not in d and "cpu_baseline" not in d and "bench.py detail: " not in r.stderr
+        assert sorted(os.listdir(tmp_path / run)) == ["flow.npy"]
+        outs.append(np.load(tmp_path / run / "flow.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (B, 68, 120, 2) and np.array_equal(outs[0], outs[1])
+    spec = importlib.util.spec_from_file_location("fotg_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    I0, I1 = bench.synth_batch(B, 1234 + 97 * ((K - 1) % D), torch.device("cuda"))          # the slot the last step ran on
+    op = F.operating_point(2, 1920, 1)
+    ofc = OFClass(op, F.img_params(width=1920, height=1080, padding=op.patch_size), max_batch=B)
+    assert np.array_equal(ofc.calc_batch(I0, I1).cpu().numpy(), outs[0])
+    ofc.close()
 
 
 def test_hoisted_division_is_the_ieee_division(tmp_path):

@@ -306,6 +306,36 @@ def test_bench_line_is_short(capsys, tmp_path, monkeypatch):
     assert det["stage_ms"] == res["stage_ms"] and "rooflines" in det and "bench.py detail: " in out.err
 
 
+def test_bench_plain_line_and_output_dump(capsys, tmp_path, monkeypatch):
+    """a plain run's emit(): the short line alone on stdout, no side file, no `detail` pointer; dump_outputs(): float32 flows
+    as flow.npy / flow_rank<r>.npy, a batch over the size cap cut to the same seeded sample of pairs every time"""
+    import json
+    import torch
+    B = _load_bench()
+    res = {"metric": "m", "value": 1.5, "unit": "frame-pairs/s", "n_gpus": 1, "steps": 7, "warmup": 2, "ms_per_step": 0.25,
+           "higher_is_better": True, "dtype": "f32", "config": {"batch_per_gpu": 64}, "rank_placement": [{"pci_bus_id": None}]}
+    monkeypatch.setattr(B, "ROOT", str(tmp_path))
+    B.emit(dict(res), detail=False)
+    out = capsys.readouterr()
+    lines = out.out.strip().splitlines()
+    assert len(lines) == 1 and out.err == "" and os.listdir(tmp_path) == []
+    s = json.loads(lines[0])
+    assert {k: s[k] for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps")} == \
+        {k: res[k] for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps")}
+    assert "detail" not in s and "one_batch_at_a_time" not in s
+    flows = torch.arange(6 * 4 * 5 * 2, dtype=torch.float32).reshape(6, 4, 5, 2)
+    B.dump_outputs(str(tmp_path / "d"), flows, 0, 1)
+    B.dump_outputs(str(tmp_path / "d"), flows, 1, 2)
+    f = np.load(tmp_path / "d" / "flow.npy")
+    assert f.dtype == np.float32 and np.array_equal(f, flows.numpy()) and (tmp_path / "d" / "flow_rank1.npy").exists()
+    monkeypatch.setattr(B, "DUMP_MAX_BYTES", 3 * flows[0].numel() * 4 + 1)
+    B.dump_outputs(str(tmp_path / "s"), flows, 0, 1)
+    B.dump_outputs(str(tmp_path / "t"), flows, 0, 1)
+    s1, s2 = np.load(tmp_path / "s" / "flow.npy"), np.load(tmp_path / "t" / "flow.npy")
+    assert s1.shape == (3, 4, 5, 2) and np.array_equal(s1, s2)
+    assert all(any(np.array_equal(x, y) for y in flows.numpy()) for x in s1)
+
+
 def test_cpp_flow_writers_match_the_python_ones(tmp_path):
     """include/fotg/flowio.h: OFC::SaveFlowFile / OFC::SavePFMFile (kroeger/run_dense.cpp:16-81) write the bytes flowonthego_amd.flo
     writes (whose .flo layout is pinned against the reference's golden file in tests/test_oracle.py)"""

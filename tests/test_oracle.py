@@ -1,11 +1,47 @@
 """CPU tests of the oracle itself: pinned against (1) the reference's golden .flo, (2) golden vectors
-produced by the reference's own FDF code (tests/golden/fdf_ref_*.npz), (3) oracle/_ref live when present."""
+produced by the reference's own FDF code (tests/golden/fdf_ref_*.npz), (3) oracle/_ref live when present, else the
+outputs it gave for the same inputs (tests/golden/fdf_ref_live.npz)."""
+import os
+
 import numpy as np
 import pytest
 
-from conftest import load_fdf, synth_pair
+from conftest import GOLDEN, load_fdf, synth_pair
 from oracle import oracle as O
 from oracle import fdf_ref as R
+
+
+class RefCalls:
+    """The reference FDF library for the live-reference tests.  Where oracle/_ref is built, every call runs the live library and
+    its outputs must equal the ones stored in tests/golden/fdf_ref_live.npz; elsewhere the call's inputs must equal the stored
+    inputs and the stored outputs of the live library are returned.  tests/golden/make_golden.py records the file by running
+    these tests with the library present (`recorded`)."""
+    PATH = os.path.join(GOLDEN, "fdf_ref_live.npz")
+
+    def __init__(self):
+        self.stored = np.load(self.PATH) if os.path.exists(self.PATH) else None
+        self.recorded = {}
+
+    def __call__(self, key, noc, method, arrays, **kw):
+        if R.available(noc):
+            out = getattr(R.FdfRef(noc), method)(*arrays, **kw)
+            out = out if isinstance(out, tuple) else (out,)
+            for i, a in enumerate(arrays):
+                self.recorded["%s/in%d" % (key, i)] = np.asarray(a)
+            for i, a in enumerate(out):
+                self.recorded["%s/out%d" % (key, i)] = np.asarray(a)
+                if self.stored is not None:
+                    assert np.array_equal(self.stored["%s/out%d" % (key, i)], a), (key, i)
+            return out
+        assert self.stored is not None, "neither oracle/_ref nor %s" % self.PATH
+        for i, a in enumerate(arrays):
+            assert np.array_equal(self.stored["%s/in%d" % (key, i)], a), (key, i)
+        return tuple(self.stored["%s/out%d" % (key, i)] for i in range(sum(k.startswith(key + "/out") for k in self.stored.files)))
+
+
+REF = RefCalls()
+VARREF_LIVE_CASES = [(1, 30, 17), (1, 37, 19), (3, 33, 18), (1, 120, 68)]
+DEPTH_LIVE_CASES = [(1, 30, 17, 0), (1, 37, 19, 1), (3, 33, 18, 0), (1, 120, 68, 0)]
 
 
 def epe(a, b):
@@ -54,12 +90,12 @@ def test_golden_flo(alley, alley_golden_flow):
 
 def _oracle_lk_with_reference_fdf(f0, f1, slow_solver):
     """the oracle's pyramid + LK + densification, with the refinement of every level done by the LIVE reference FDF library
-    (oracle/_ref: kroeger/FDF1.0.1 compiled unmodified) sequenced as VarRefClass::RefLevelOF does -> full-resolution flow"""
+    (oracle/_ref: kroeger/FDF1.0.1 compiled unmodified, or its stored outputs: RefCalls) sequenced as VarRefClass::RefLevelOF
+    does -> full-resolution flow"""
     p = O.op_point(2, f0.shape[1], 1)
     h, w = f0.shape
     wp, hp, padw, padh = O.padded_size(w, h, p.sc_f)
     P0, P1 = O.Pyramid(O.pad_frame(f0, p.sc_f), p.sc_f, p.ps), O.Pyramid(O.pad_frame(f1, p.sc_f), p.sc_f, p.ps)
-    ref = R.FdfRef(1)
     prev = None
     for sl in range(p.sc_f, p.sc_l - 1, -1):
         lw, lh = P0.level_wh(sl)
@@ -70,12 +106,12 @@ def _oracle_lk_with_reference_fdf(f0, f1, slow_solver):
         g.optimize(P1.im[sl])
         fl = g.aggregate()
         crop = lambda a: np.ascontiguousarray(a[p.ps:p.ps + lh, p.ps:p.ps + lw, 0])[None]
-        ox, oy = ref.ref_level_of(crop(P0.im[sl]), crop(P1.im[sl]), fl[..., 0].copy(), fl[..., 1].copy(), sl, slow_solver=slow_solver)
+        ox, oy = REF("lk_half/%s/L%d" % ("slow" if slow_solver else "fast", sl), 1, "ref_level_of",
+                     (crop(P0.im[sl]), crop(P1.im[sl]), fl[..., 0].copy(), fl[..., 1].copy()), lvl=sl, slow_solver=slow_solver)
         prev = np.stack([ox, oy], -1)
     return O.upsample_crop(prev, p.sc_l, padw, padh, w, h)
 
 
-@pytest.mark.skipif(not R.available(1), reason="oracle/_ref not built (reference tree absent)")
 def test_lk_half_with_live_reference_refinement(alley):
     """a second, independent agreement of the LK half with the real kroeger build: with the live
     reference FDF library refining every level, the oracle's pyramid + LK + densification give O.full_flow bit for bit; and
@@ -125,8 +161,7 @@ def test_fdf_golden_vectors(noc):
         assert np.array_equal(out[..., 0], c["out_x"]) and np.array_equal(out[..., 1], c["out_y"]), name
 
 
-@pytest.mark.skipif(not R.available(1), reason="oracle/_ref not built (reference tree absent)")
-@pytest.mark.parametrize("noc,w,h", [(1, 30, 17), (1, 37, 19), (3, 33, 18), (1, 120, 68)])
+@pytest.mark.parametrize("noc,w,h", VARREF_LIVE_CASES)
 def test_varref_vs_live_reference(noc, w, h):
     """random smooth inputs through the live reference FDF library vs the oracle, incl. widths that are
     not multiples of 4 (stride padding) -- bit-exact"""
@@ -136,14 +171,15 @@ def test_varref_vs_live_reference(noc, w, h):
     im2 = f1.reshape(h, w, noc).transpose(2, 0, 1).copy()
     wx = (0.7 + 0.3 * rng.standard_normal((h, w))).astype(np.float32)
     wy = (-0.4 + 0.3 * rng.standard_normal((h, w))).astype(np.float32)
-    ox, oy = R.FdfRef(noc).ref_level_of(im1, im2, wx, wy, 3)
+    key = "varref/%d_%d_%d" % (noc, w, h)
+    ox, oy = REF(key + "/fast", noc, "ref_level_of", (im1, im2, wx, wy), lvl=3)
     p = O.op_point(2, 1024, noc)
     ps = 8
     padlvl = lambda a: np.pad(a.transpose(1, 2, 0), ((ps, ps), (ps, ps), (0, 0)), mode="edge")
     out = O.varref(padlvl(im1), padlvl(im2), w, h, 3, p, np.stack([wx, wy], -1))
     assert np.array_equal(out[..., 0], ox) and np.array_equal(out[..., 1], oy)
     # SURVEY row a17': sor_coupled_slow_but_readable (solver.c:19-72), the reference's OpenMP-build solver run serially
-    sx, sy = R.FdfRef(noc).ref_level_of(im1, im2, wx, wy, 3, slow_solver=True)
+    sx, sy = REF(key + "/slow", noc, "ref_level_of", (im1, im2, wx, wy), lvl=3, slow_solver=True)
     out = O.varref(padlvl(im1), padlvl(im2), w, h, 3, p, np.stack([wx, wy], -1), sor_mode=2)
     assert np.array_equal(out[..., 0], sx) and np.array_equal(out[..., 1], sy)
     assert not np.array_equal(sx, ox)
@@ -295,8 +331,7 @@ def test_depth_fdf_golden_vectors(noc):
             assert (out <= 0).all() if camlr == 0 else (out >= 0).all()
 
 
-@pytest.mark.skipif(not R.available(1), reason="oracle/_ref not built (reference tree absent)")
-@pytest.mark.parametrize("noc,w,h,camlr", [(1, 30, 17, 0), (1, 37, 19, 1), (3, 33, 18, 0), (1, 120, 68, 0)])
+@pytest.mark.parametrize("noc,w,h,camlr", DEPTH_LIVE_CASES)
 def test_depth_varref_vs_live_reference(noc, w, h, camlr):
     rng = np.random.default_rng(w * 100 + h)
     f0, f1 = synth_pair(h, w, seed=w, noc=noc, shift=(-0.7 if camlr == 0 else 0.7, 0.0))
@@ -304,8 +339,7 @@ def test_depth_varref_vs_live_reference(noc, w, h, camlr):
     im2 = f1.reshape(h, w, noc).transpose(2, 0, 1).copy()
     wx = (0.7 + 0.3 * rng.standard_normal((h, w))).astype(np.float32)
     wx = -np.abs(wx) if camlr == 0 else np.abs(wx)
-    dump = {}
-    ox = R.FdfRef(noc).ref_level_de(im1, im2, wx, 3, camlr=camlr, dump=dump)
+    ox, = REF("depth/%d_%d_%d_%d" % (noc, w, h, camlr), noc, "ref_level_de", (im1, im2, wx), lvl=3, camlr=camlr)
     p = depth_params(2, 1024, noc)
     out = O.varref_depth(_padlvl(im1), _padlvl(im2), w, h, 3, p, wx[..., None], camlr)
     assert np.array_equal(out[..., 0], ox)

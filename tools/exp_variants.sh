@@ -5,7 +5,7 @@ for lib in "" tools/exp/libfotg_*.so ""; do
   [ -n "$lib" ] && [ ! -e "$lib" ] && continue
   export FOTG_EXPERIMENTAL_LIB=${lib:+$PWD/$lib}; [ -z "$lib" ] && unset FOTG_EXPERIMENTAL_LIB
   echo -n "$(basename ${lib:-libfotg.so}): "
-  timeout 600 python bench.py --no-cpu-baseline --windows 9 >/dev/null 2>&1; python -c "
+  timeout 600 python bench.py --full --no-cpu-baseline --windows 9 >/dev/null 2>&1; python -c "
 import json
 r=json.load(open('gpurun_out/bench_detail.json'))
 d=r.get('roofline_dominant',{})
