@@ -12,6 +12,9 @@ def __getattr__(name):
     if name in ("OFClass", "PatGridClass", "VarRefClass", "gradient_magnitude"):
         from . import oflow
         return getattr(oflow, name)
+    if name in ("flow_to_color", "write_png", "color_wheel"):
+        from . import color
+        return getattr(color, name)
     if name == "FlowPipeline":
         from .pipeline import FlowPipeline
         return FlowPipeline

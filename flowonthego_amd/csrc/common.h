@@ -24,6 +24,16 @@ struct LevelGeom {
   float lb, ubw, ubh;
 };
 
+// a context's final-scale geometry as fotg_upsample_crop uses it, for host code outside fotg_capi.hip (fotg_color.hip)
+struct CtxUpsampleGeom {
+  int device, max_batch, nch, sc_l;
+  int wl, hl;        // coarse flow size (the padded frame >> sc_l)
+  int x0, y0;        // crop offsets: padw / 2, padh / 2
+  int w_org, h_org;
+};
+int ctx_upsample_geom(const fotg_ctx *c, CtxUpsampleGeom *g);
+void set_last_hip_error(int e);
+
 __host__ __device__ inline int clampi(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 __host__ __device__ inline int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 

@@ -155,6 +155,19 @@ static void fill_geom(const fotg_params &p, int Wp, int Hp, int l, LevelGeom &g)
   g.nop = g.nopw * g.noph;
 }
 
+// for the colour code's translation unit (fotg_color.hip, flowcolor.hip.h): what fotg_upsample_crop launches with, and the
+// thread's last HIP error
+namespace fotg {
+int ctx_upsample_geom(const fotg_ctx *c, CtxUpsampleGeom *g)
+{
+  if (!c || !g) return FOTG_ERR_ARG;
+  const LevelGeom &l = c->geom[c->p.sc_l];
+  *g = {c->device, c->max_batch, c->nch, c->p.sc_l, l.w, l.h, c->padw / 2, c->padh / 2, c->w_org, c->h_org};
+  return FOTG_OK;
+}
+void set_last_hip_error(int e) { g_last_hip = e; }
+}  // namespace fotg
+
 extern "C" {
 
 const char *fotg_version(void) { return "fotg-mi355x 0.1 (gfx950)"; }

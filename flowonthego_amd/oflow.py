@@ -188,6 +188,11 @@ class OFClass:
         check(lib().fotg_upsample_crop(self._h, n, _ptr(flow), _ptr(out), _stream(self.device)))
         return out
 
+    def upsample_crop_color(self, flow, maxmotion=None, out=None, stats=False):
+        """the Middlebury colour code of upsample_crop(flow), fused: uint8 (n, h_org, w_org, 3) -- flowonthego_amd.color"""
+        from .color import upsample_crop_color
+        return upsample_crop_color(self, flow, maxmotion=maxmotion, out=out, stats=stats)
+
     # -- pyramid (src/oflow.cpp:182-207 ConstructImgPyramids) -----------------------------------------------
     def ConstructImgPyramids(self, I0, I1):
         n = I0.shape[0]

@@ -228,6 +228,20 @@ int fotg_upsample_crop(fotg_ctx *ctx, int n, const float *flow, float *out, void
 int fotg_gradient_magnitude(int device, int n, const float *frames, int w_org, int h_org, int channels, int sc_f, float *out, void *stream);
 int fotg_gradient_magnitude_u8(int device, int n, const unsigned char *frames, int w_org, int h_org, int channels, int sc_f, float *out, void *stream);
 
+/* Middlebury colour code of a flow (flow_code/C/color_flow.cpp MotionToColor + colorcode.cpp computeColor).
+ * flow: n x h x w x 2 f32 (device); rgb: n x h x w x 3 uint8 (device), R, G, B per pixel (the byte order of the reference's PNG).
+ * Normalised PER IMAGE by maxrad = the largest |(u, v)| over its known vectors, or by maxmotion when maxmotion > 0 (a maxrad of 0
+ * becomes 1); unknown vectors (|u| > 1e9, |v| > 1e9 or NaN, flowIO.cpp unknown_flow) are black.
+ * stats: NULL or n x 5 f32 (device): maxrad, minu, maxu, minv, maxv over the known vectors -- the values color_flow prints, with
+ * its initial values -1 / 999 / -999 where an image has none.  Asynchronous on `stream`.  Bit-identical to the reference's
+ * arithmetic except the angle: the correctly rounded f32 of atan2 instead of glibc's atan2f.
+ * FOTG_ERR_ARG: n < 1, w or h <= 0, a null flow or rgb. */
+int fotg_flow_color(int device, int n, const float *flow, int w, int h, float maxmotion, unsigned char *rgb, float *stats, void *stream);
+/* The same from the context's coarse flow (n x hl x wl x 2, the layout of fotg_calc_batch's outflow), upsampled and cropped on the
+ * fly: rgb (n x h_org x w_org x 3) == fotg_flow_color(fotg_upsample_crop(flow)) byte for byte, without writing the full-resolution
+ * flow.  FOTG_ERR_ARG: n < 1 or n > max_batch, a null pointer, a depth-mode context (one channel: no colour code for it). */
+int fotg_upsample_crop_color(fotg_ctx *ctx, int n, const float *flow, float maxmotion, unsigned char *rgb, float *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,

@@ -32,6 +32,8 @@ def arg(t, first_handle, name):
         return vp(None)
     if t in (C.c_int, C.c_long):
         return t(int(rng.choice(ints)))
+    if t is C.c_float:
+        return t(float(rng.choice([0.0, -1.0, 1.0, 1e30, float("nan")])))
     if t is C.c_char_p:
         return C.c_char_p(rng.choice([b"", b"a11", b"nonsense", b"stamps_ptr"]))
     if hasattr(t, "_type_"):                      # POINTER(x): null, or a small scratch object
