@@ -304,10 +304,14 @@ __global__ __launch_bounds__(64, lk_min_waves(PS * PS * NOC, SHW, LPP)) void lk_
     float *hp = a.hes + ((size_t)pair * a.g.nop + IP) * 3;
     hp[0] = H00; hp[1] = H01; hp[2] = H11;
   }
-  // Cholesky factor of the (constant) Hessian, hoisted out of the loop: same values every iteration
-  const float L00 = sqrtf(H00);
-  const float L10 = DEPTH ? 0.f : H01 / L00;
-  const float L11 = DEPTH ? 1.f : sqrtf(H11 - L10 * L10);
+  // Cholesky factor of the (constant) Hessian, hoisted out of the loop: same values every iteration.  Eigen's LLT (oracle
+  // dis_llt2) stops at the first pivot <= 0 and solves with the entries it has not factored: h00 <= 0 leaves all of H as it
+  // is, h11 - l10^2 <= 0 (every rank-deficient patch: ramps, straight edges) leaves l11 = h11
+  const bool F0 = H00 <= 0.f;
+  const float L00 = F0 ? H00 : sqrtf(H00);
+  const float L10 = DEPTH ? 0.f : (F0 ? H01 : H01 / L00);
+  const float X11 = H11 - L10 * L10;
+  const float L11 = DEPTH ? 1.f : ((F0 || X11 <= 0.f) ? H11 : sqrtf(X11));
   // The solve divides by L00 and L11 four times per iteration: the reciprocal refinement of those divisions is hoisted
   // (fdiv_hoist.h); a quotient outside the guarded range sends the whole wave through the compiler's divisions instead.
   const InvDiv iL00 = make_invdiv(L00), iL11 = make_invdiv(L11);
@@ -439,7 +443,7 @@ __global__ __launch_bounds__(64, lk_min_waves(PS * PS * NOC, SHW, LPP)) void lk_
       }
       float nPTX = RX + nP0, nPTY = RY + nP1;
       const float ddx = STX - nPTX, ddy = STY - nPTY;
-      const bool bad = !(isfinite(x0) && isfinite(x1));  // oracle definition D3
+      const bool bad = !(isfinite(x0) && isfinite(x1));  // oracle definition D3 (non-finite input data only)
       // :199-208; norm > outlier as a test on the squared norm: a.outlier_sq is the largest float whose correctly rounded
       // square root is <= outlier (found on the host), and sqrtf is monotonic
       const bool reset = bad || ddx * ddx + ddy * ddy > a.outlier_sq ||

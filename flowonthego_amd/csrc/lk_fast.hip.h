@@ -154,9 +154,11 @@ __global__ __launch_bounds__(64, lkf_min_waves(PS, NOC, LPP, R)) void lk_fast_ke
       float *hp = a.hes + ((size_t)pair * a.g.nop + IP) * 3;
       hp[0] = H00; hp[1] = H01; hp[2] = H11;
     }
-    // H^-1 = L^-T L^-1 from the Cholesky factor the reference solves with (patch.cpp:184); a singular / indefinite H gives
-    // non-finite entries, i.e. a non-finite update: the patch is reset at its first iteration, as in the exact kernel
-    const float L00 = sqrtf(H00), L10 = H01 / L00, L11 = sqrtf(H11 - L10 * L10);
+    // H^-1 = L^-T L^-1 from the Cholesky factor the reference solves with (patch.cpp:184), with Eigen's early return at a
+    // pivot <= 0 (unfactored entries kept, as lk.hip.h / the oracle's dis_llt2): the formula holds for any lower-triangular L
+    const bool F0 = H00 <= 0.f;
+    const float L00 = F0 ? H00 : sqrtf(H00), L10 = F0 ? H01 : H01 / L00, X11 = H11 - L10 * L10;
+    const float L11 = (F0 || X11 <= 0.f) ? H11 : sqrtf(X11);
     const float ia = 1.0f / L00, ib = 1.0f / L11, m = -L10 * ia * ib;
     IH00 = ia * ia + m * m; IH01 = m * ib; IH11 = ib * ib;
     K0 = -(IH00 * C0 + IH01 * C1); K1 = -(IH01 * C0 + IH11 * C1);          // dp = H^-1 (S - C) = H^-1 S + K

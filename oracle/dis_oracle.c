@@ -11,8 +11,9 @@
  *        version dependent; Eigen is not part of the reference tree).
  *   (D2) a patch whose start position is outside the valid region keeps an all-zero pweight
  *        (reference: pweight is left as it was allocated -- uninitialised, patch.cpp:135-141).
- *   (D3) a non-finite LK update is treated like an outlier (reset to p_in, stop).  The reference
- *        would convert NaN to int (undefined behaviour, patch.cpp:345-348).
+ *   (D3) a non-finite LK update is treated like an outlier (reset to p_in, stop).  With Eigen's LLT semantics (dis_llt2:
+ *        a failed factorisation still solves with finite pivots) finite frames never give one; only NaN / inf input data
+ *        does, where the reference would convert NaN to int (undefined behaviour, patch.cpp:345-348).
  *   (D5) InitializeFromCoarserOF clamps the half-resolution index into the coarser array (the reference reads
  *        one row / column out of bounds when the level size is odd, which only `initflow` can make happen).
  *   (D4) 2x2 half-resolution = ((a+c)+(b+d))*0.25 (rows first); for 8-bit valued input every
@@ -245,17 +246,22 @@ float dis_sum(const float *v, int n, int noc)
     return acc;
   }
   if (g_sum_order == 2) {
-    /* Eigen-style vectorised redux with 4-float packets (SSE, the reference's -msse4 build): two packet accumulators over
-     * alternating packets, added, then the horizontal sum (a0 + a2) + (a1 + a3) (movehl / shuffle form of predux) */
-    float p0[4], p1[4];
-    for (int k = 0; k < 4; ++k) { p0[k] = v[k]; p1[k] = n >= 8 ? v[4 + k] : 0.0f; }
-    int e = 8;
-    for (; e + 8 <= n; e += 8) for (int k = 0; k < 4; ++k) { p0[k] = p0[k] + v[e + k]; p1[k] = p1[k] + v[e + 4 + k]; }
-    if (e + 4 <= n) { for (int k = 0; k < 4; ++k) p0[k] = p0[k] + v[e + k]; e += 4; }
+    /* Eigen-style vectorised redux with 4-float packets (SSE, the reference's -msse4 build; Eigen 3.3 Core/Redux.h,
+     * LinearVectorizedTraversal): two packet accumulators over alternating packets, added; then a trailing odd packet; then
+     * the horizontal sum (a0 + a2) + (a1 + a3) (movehl / shuffle form of predux); then the scalar tail */
+    if (n < 4) { float r = v[0]; for (int e = 1; e < n; ++e) r = r + v[e]; return r; }
+    const int al2 = (n / 8) * 8, al = (n / 4) * 4;
     float q[4];
-    for (int k = 0; k < 4; ++k) q[k] = n >= 8 ? p0[k] + p1[k] : p0[k];
+    for (int k = 0; k < 4; ++k) q[k] = v[k];
+    if (al > 4) {
+      float p1[4];
+      for (int k = 0; k < 4; ++k) p1[k] = v[4 + k];
+      for (int e = 8; e < al2; e += 8) for (int k = 0; k < 4; ++k) { q[k] = q[k] + v[e + k]; p1[k] = p1[k] + v[e + 4 + k]; }
+      for (int k = 0; k < 4; ++k) q[k] = q[k] + p1[k];
+      if (al > al2) for (int k = 0; k < 4; ++k) q[k] = q[k] + v[al2 + k];
+    }
     float r = (q[0] + q[2]) + (q[1] + q[3]);
-    for (; e < n; ++e) r = r + v[e];
+    for (int e = al; e < n; ++e) r = r + v[e];
     return r;
   }
   if (g_sum_order == 3) return dis_sum_pairwise(v, n);
@@ -404,6 +410,23 @@ static void patch_bil(const dis_grid *g, const dis_params *p, const float *img, 
   }
 }
 
+/* patch.cpp:184 Hes.llt(): Eigen's unblocked Cholesky (Cholesky/LLT.h, llt_inplace<float, Lower>::unblocked) STOPS at the
+ * first column k whose pivot x = a_kk - |l_k,0:k|^2 is <= 0, leaving that diagonal entry and everything below / right of it
+ * unfactored, and solve() uses the matrix as it stands (the failure is only reported through info()).  So:
+ *   h00 <= 0:              L = [h00 0; h01 h11]       (nothing factored)
+ *   h11 - l10^2 <= 0:      L = [sqrt(h00) 0; l10 h11]
+ * A NaN pivot is not <= 0 and goes through sqrt.  The second case is every rank-deficient patch whose Hessian the
+ * determinant test (:78-82) lifts by only 1e-10: linear ramps, straight edges, one-directional texture. */
+static inline float dis_llt_diag(float x) { return x <= 0.0f ? x : sqrtf(x); }
+static inline void dis_llt2(float h00, float h01, float h11, float *l00, float *l10, float *l11)
+{
+  if (h00 <= 0.0f) { *l00 = h00; *l10 = h01; *l11 = h11; return; }
+  *l00 = sqrtf(h00);
+  *l10 = h01 / *l00;
+  const float x = h11 - *l10 * *l10;
+  *l11 = x <= 0.0f ? h11 : sqrtf(x);
+}
+
 /* patchgrid.cpp:134-141 Optimize -> patch.cpp:159-212 OptimizeIter, :120-156 OptimizeStart,
  * :264-284 OptimizeComputeErrImg, :223-261 LossComputeErrorImage (costfct 0 L2, 1 L1, 2 pseudo-Huber) */
 void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float *trace)
@@ -436,15 +459,14 @@ void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float 
       cnt++;
       dp0 = dis_dot(Tx, pdiff, nv, noc, scr);                        /* :178-179 */
       if (g->depth) {                                                /* :181, :184 with the 1x1 Hessian: L = sqrt(H) */
-        float l00 = sqrtf(h00);
+        float l00 = dis_llt_diag(h00);
         float y0 = dp0 / l00;
         dp0 = y0 / l00; dp1 = 0.0f;
       } else {
       dp1 = dis_dot(Ty, pdiff, nv, noc, scr);
-      {                                                              /* :184 Hes.llt().solve() */
-        float l00 = sqrtf(h00);
-        float l10 = h01 / l00;
-        float l11 = sqrtf(h11 - l10 * l10);
+      {                                                              /* :184 Hes.llt().solve() (Eigen LLT, see dis_llt2) */
+        float l00, l10, l11;
+        dis_llt2(h00, h01, h11, &l00, &l10, &l11);
         float y0 = dp0 / l00;
         float y1 = (dp1 - l10 * y0) / l11;
         float x1 = y1 / l11;
@@ -460,7 +482,7 @@ void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float 
       ptx = rx + p0; pty = ry + p1;
       {
         float ddx = stx - ptx, ddy = sty - pty;
-        int bad = !(isfinite(dp0) && isfinite(dp1));                 /* (D3) */
+        int bad = !(isfinite(dp0) && isfinite(dp1));                 /* (D3): only non-finite input data gets here */
         if (bad || sqrtf(ddx * ddx + ddy * ddy) > outlier ||         /* :199-208 */
             ptx < g->lb || pty < g->lb || ptx > g->ubw || pty > g->ubh) {
           p0 = pin0; p1 = pin1; ptx = rx + p0; pty = ry + p1;

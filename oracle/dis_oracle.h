@@ -12,10 +12,12 @@
  *     oracle/_ref/libfdf_ref_{gray,rgb}.so (oracle/Makefile, target `ref`);
  *   - the whole pipeline is checked against the reference's only golden result,
  *     kroeger/flows/alley_0001.flo (tests/golden/), mean EPE <= 0.05 px;
- *   - the C++ stages (patch.cpp, patchgrid.cpp, oflow.cpp) need Eigen, which this image lacks, so
- *     they cannot be built here; the OpenCV calls of run_dense.cpp likewise.  Their restatement
- *     is pinned only through the golden .flo.  Summation order of the per-patch reductions is
- *     Eigen-version dependent in the reference; the order used here is documented at dis_sum().
+ *   - the C++ stages (patch.cpp, patchgrid.cpp, oflow.cpp, refine_variational.cpp) are compiled unmodified
+ *     against the project's minimal Eigen (oracle/eigen_min) into oracle/_ref/libkroeger_*.so; with the
+ *     Eigen-style sum order (dis_set_sum_order(2)) this restatement equals them bit for bit
+ *     (tests/test_kroeger_pin.py).  The OpenCV calls of run_dense.cpp are not built; the pyramid is
+ *     pinned only through the golden .flo.  The default order of the per-patch reductions (D1) is
+ *     documented at dis_sum().
  */
 #ifndef DIS_ORACLE_H
 #define DIS_ORACLE_H
