@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <map>
 #include <mutex>
 #include <new>
 #include "common.h"
@@ -76,8 +77,6 @@ struct FotgTune {
 static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 #ifdef FOTG_DEBUG
-#include <map>
-#include <mutex>
 static std::map<void *, void *> g_dbg_base;      // user pointer -> allocation base (FOTG_DEBUG_GUARD)
 static std::mutex g_dbg_mu;
 static hipError_t fotg_dbg_free(void *p)
@@ -792,245 +791,281 @@ int fotg_grid_read(fotg_ctx *c, int l, int pair, float *p_iter, float *pweight, 
 /* variational refinement                                                                           */
 /* ------------------------------------------------------------------------------------------------ */
 }  // extern "C"
-template <int K, int P>
-static void launch_sor(const VrArgs &a, int n, int sweeps, float omega, hipStream_t s)
+
+// ---- which kernels run a level: plan_level (pure: it launches and allocates nothing), then the launches (varref_impl) ----------
+
+#define FOTG_LDS_MAX (160 * 1024)       // LDS of a CU: the most dynamic LDS a kernel can opt in to
+constexpr int kSyncMinDiag = 24;        // fewest diagonals (S) the barrier-stepped solver waves (sor_sync_wave) are built for
+constexpr int kVrP = 8, kVrU = 32;      // prefetch depth / steps per loop trip of the LDS solvers (stream, pipe, fused)
+
+// the kernel of one sor_coupled call: vr_sor_stream_kernel <72, 70> / <100, 98> (65..96 rows, diagonals stream through LDS rings),
+// vr_sor_pipe_kernel (the whole (du,dv) in LDS), vr_sor_tile_kernel (tall levels, varref_tiles.hip.h), vr_sor_tall_kernel (a sweep per
+// launch), vr_sor_kernel <K, P> (single wave), the last two with FOTG_SOR_POINT's update, vr_rb_halfsweep_kernel
+enum SorKind { SOR_NONE, SOR_STREAM70, SOR_STREAM98, SOR_PIPE, SOR_TILES, SOR_TALL, SOR_WAVE, SOR_POINT_TALL, SOR_POINT, SOR_REDBLACK };
+struct SorPlan {
+  SorKind kind;
+  int nsweeps, nbands, lds;             // stream, pipe: VrArgs::nsweeps, row bands of the solver waves, dynamic LDS bytes
+  int P;                                // SOR_WAVE: prefetch depth
+};
+// vr_inner_fused_kernel, the whole level in one launch: gray levels of 1025..2048 (1024 threads) / <= 1024 pixels (512) with the
+// per-pixel inputs in registers; the system cells in LDS; the system cells in global memory
+enum FusedKind { FUSED_NONE, FUSED_RES1024, FUSED_RES, FUSED_CL, FUSED_CGLOBAL };
+struct VrPlan {
+  FusedKind fused;                      // != FUSED_NONE: the whole level is this one launch of nsweeps and lds bytes, nothing below applies
+  int nsweeps, lds;
+  bool merged_first;                    // the set-up launch builds the system of the first inner iteration
+  int zsync_n;                          // sync words of the tile pipeline the set-up / data-term launches clear for the launch behind them
+  bool levelpipe; unsigned lp_nwg;      // the fixed-point loop is one vr_level_pipe_kernel launch of lp_nwg workgroups
+  int excl;                             // its dynamic LDS: enough to keep it alone on a CU, or 0
+  SorPlan sor;                          // each sor_coupled call of the fixed-point loop (and fotg_bench_sor_call)
+};
+
+// (du,dv) of a level in LDS: header + (S + 2) rows of RPD float2 cells (varref.hip.h, FOTG_LDS_HDR)
+static int d_lds_bytes(const VrArgs &a) { return 128 + (a.S + 2) * a.RPD * (int)sizeof(float2); }
+// the fused kernel adds the smoothness plane and, with_c, the skewed system cells
+static int fused_lds_bytes(const VrArgs &a, bool with_c)
 {
-  constexpr int U = (K <= 2) ? (P >= 8 ? 64 : 8 * P) : (K <= 4 ? 4 * P : P);     // steps per loop trip
-  vr_sor_kernel<K, P, U><<<n, 64, 0, s>>>(a, sweeps, omega);
+  return d_lds_bytes(a) + ((a.w * a.h + 3) / 4) * 16 + (with_c ? (a.SC * a.RP + 1) * 32 : 0);
 }
 
-// Row bands of the barrier-stepped solver waves (sor_sync_wave): bands of <= 64 rows, one lane per row, one wave per (sweep, band).
-static void set_bands(VrArgs &b, int sweeps)
+// Row bands of the barrier-stepped solver waves (stream, pipe and fused kernels): bands of <= 64 rows, one lane per row, one wave per
+// (sweep, band), at most four sweeps and eight waves.  0 = the level does not fit them.
+static int sync_bands(const VrArgs &a, int sweeps)
 {
-  b.nbands = 0; b.band_rows = 0; b.band_mode = 0;
-  const int nb = (b.h + 63) / 64;
-  if (sweeps * nb > 8 || sweeps > 4) return;
-  b.nbands = nb;
-  b.band_rows = (b.h + nb - 1) / nb;
+  const int nb = (a.h + 63) / 64;
+  return sweeps >= 1 && sweeps <= 4 && sweeps * nb <= 8 && a.S >= kSyncMinDiag ? nb : 0;
+}
+static VrArgs with_bands(const VrArgs &a, int nsweeps, int nbands)
+{
+  VrArgs b = a;
+  b.nsweeps = nsweeps;
+  b.nbands = nbands;
+  b.band_rows = (a.h + nbands - 1) / nbands;
   b.band_mode = 3;
+  return b;
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: cache what was set per device
-static std::mutex g_lds_mu;             // contexts / pipes driven from different host threads share the per-kernel caches below
-static bool ensure_dyn_lds(const void *fn, int lds, int (&set)[32])
+// dynamic LDS of the streaming solver in geometry <RD, RCW> (<= RCW - 1 rows per diagonal), or 0 when the level does not fit it
+template <int RD, int RCW>
+static int stream_lds(const VrArgs &a, int nsweeps)
+{
+  constexpr int M = FOTG_SYNC_M;
+  using GEO = StreamGeom<RD, RCW>;
+  if (a.RP < 64 || a.RP + 1 > RCW || a.RPD > RD || (a.RPD & 1) || a.S < 2 * kVrU) return 0;
+  if (nsweeps > 3 || a.h + 2 > a.RPD) return 0;
+  const int DS = ((M + 2 + M - 1) / M) * M;
+  const int omax = nsweeps > 0 ? (nsweeps - 1) * DS : 0;
+  const int RDN = M * (GEO::LI + omax / M + 1 + 1), RCN = RDN - M;
+  const int lds = RCN * GEO::CSLOT + RDN * GEO::DB + GEO::DB;
+  return lds <= FOTG_LDS_MAX ? lds : 0;
+}
+
+// the lexicographic solver of a level (pipe_sweeps, nosor: plan_level's timing switches)
+static SorPlan plan_sor(const fotg_ctx *c, int l, int pipe_sweeps, bool nosor)
+{
+  const VrArgs &a = c->vra[l];
+  const int path = c->tune.vr_path;     // FOTG_VR_PATH=1 (tests, and the recompute of a stalled tile pipeline): no LDS solver, no inter-workgroup waits
+  if (const int nb = path != 1 ? sync_bands(a, pipe_sweeps) : 0) {
+    const int nsw = nosor ? 0 : pipe_sweeps;
+    if (c->tune.vr_stream) {            // (FOTG_VR_STREAM=0: the pipe kernel instead; tests)
+      if (const int lds = stream_lds<72, 70>(a, nsw)) return {SOR_STREAM70, nsw, nb, lds, 0};
+      if (const int lds = stream_lds<100, 98>(a, nsw)) return {SOR_STREAM98, nsw, nb, lds, 0};
+    }
+    if (d_lds_bytes(a) <= 150 * 1024) return {SOR_PIPE, nsw, nb, d_lds_bytes(a), 0};
+  }
+  if (path == 1 && a.h > 1024) return {SOR_TALL};
+  if (path != 1 && c->vrX[l] && c->tileSync) return {SOR_TILES};      // (fotg_create gave the level the tile pipeline's buffers)
+  // prefetch depth: as deep as the register budget of K rows per lane allows, and 2P+2 <= S (ring never runs ahead into rows the
+  // current sweep has not rewritten yet)
+  int P = a.K == 1 ? 16 : a.K == 2 ? 8 : a.K <= 4 ? 4 : 1;
+  while (P > 1 && P > (a.S - 2) / 2) P >>= 1;
+  return {SOR_WAVE, 0, 0, 0, P};
+}
+
+static VrPlan plan_level(const fotg_ctx *c, int l, int n)
+{
+  const VrArgs &a = c->vra[l];
+  const int sweeps = c->p.tv_solverit, inner = c->p.tv_innerit * (l + 1), mode = c->p.sor_mode;
+  int pipe_sweeps = sweeps;             // sweeps of the stream / pipe kernels
+  bool nosor = false;                   // the barrier-stepped kernels relax nothing
+#ifdef FOTG_DEBUG
+  if (const char *e = getenv("FOTG_DEBUG_SWEEPS")) pipe_sweeps = atoi(e);     // timing experiments only (wrong results)
+  nosor = getenv("FOTG_DEBUG_NOSOR") != nullptr;                              // timing experiments only
+#endif
+  VrPlan p = {};
+  p.sor = sweeps < 1 ? SorPlan{SOR_NONE}
+        : mode == FOTG_SOR_REDBLACK ? SorPlan{SOR_REDBLACK}
+        : mode == FOTG_SOR_POINT ? SorPlan{a.h > 1024 ? SOR_POINT_TALL : SOR_POINT}      // (more rows than 64 lanes x 16: a sweep per launch)
+        : plan_sor(c, l, pipe_sweeps, nosor);
+  // small levels: the whole level (set-up stages, fixed-point loop, final w + d) in one launch, one workgroup per pair (FOTG_VR_PATH != 0:
+  // never).  One workgroup does the per-pixel phases of its pair: only worth it for small levels (measured: 60x34 yes, 120x68 no).
+  // (red-black has no dependency chain: its half-sweeps use all the workgroup's threads, and one launch per level beats 2 + inner (1 + 2
+  // sweeps) launches at any level whose (du,dv) and smoothness plane fit in LDS -- 1080p level 4 included).  A single band (<= 64 rows).
+  const int npx = a.w * a.h;
+  if (mode != FOTG_SOR_POINT && c->tune.vr_path == 0 && inner >= 1 && sync_bands(a, sweeps) == 1 && fused_lds_bytes(a, false) <= 156 * 1024 &&
+      (npx <= 3000 || mode == FOTG_SOR_REDBLACK)) {
+    p.nsweeps = nosor ? 0 : sweeps;
+    // wide, short levels whose skewed system (w + h) x h x 32 B does not fit beside (du,dv) and the smoothness plane -- e.g. 100 x 30:
+    // 133 KB -- keep it in global memory; gray levels of <= 4 pixels per thread keep their per-pixel inputs in registers over the loop
+    // (levels of more than 1024 pixels: 1024 threads, two pixels each -- 4 waves per SIMD hide the latencies of the per-pixel phases)
+    p.fused = fused_lds_bytes(a, true) > FOTG_LDS_MAX ? FUSED_CGLOBAL
+            : c->noc == 1 && npx > 1024 && npx <= 2048 ? FUSED_RES1024
+            : c->noc == 1 && npx <= 1024 ? FUSED_RES
+            : FUSED_CL;
+    p.lds = fused_lds_bytes(a, p.fused != FUSED_CGLOBAL);
+    return p;
+  }
+  // warp + first + second derivatives in one tiled launch, which also zeroes (du,dv) (refine_variational.cpp:185-186) and builds the
+  // system of the first inner iteration (unless tune.vr_first_data = 0: a data-term launch of its own)
+  p.merged_first = c->tune.vr_first_data && inner > 0;
+  // FOTG_VR_LEVELPIPE=1: the level's whole fixed-point loop as ONE pipeline launch behind the set-up launch.  At least two sweeps per
+  // call (what keeps a band's last sweep behind the data term of its neighbours), at most four (X buffers).
+  const bool tiled = c->vrX[l] && c->tileSync;
+  const int ntr = (a.h + FOTG_LP_TH - 1) / FOTG_LP_TH;
+  const long lp_words = lp_tile_words(n, c->tile_nbs) + lp_data_words(n, ntr);
+  p.levelpipe = tiled && c->tune.vr_levelpipe && n <= c->tune.lp_max_pairs && c->tune.vr_path == 0 && c->tune.vr_first_data &&
+                inner >= 1 && inner <= FOTG_LP_KMAX && sweeps >= 2 && sweeps <= 4 && ntr <= c->lp_ntr && lp_words <= c->sync_total;
+  // levels that go through the tile pipeline: the launch in front of every sor_coupled call (data term; set-up with the first data
+  // term) clears the pipeline's sync words
+  p.zsync_n = !tiled ? 0 : p.levelpipe ? (int)lp_words : (int)tile_sync_words(n, c->tile_nbs);
+  if (p.levelpipe) {
+    const int nb = (a.h + FOTG_TILE_ROWS - 1) / FOTG_TILE_ROWS;
+    p.lp_nwg = (unsigned)n * (unsigned)(inner * nb * sweeps + (inner - 1) * ntr * FOTG_LP_DW);
+    // a launch that fits the chip with one workgroup per CU asks for enough LDS to get exactly that: a solver wave that shares its
+    // SIMD with a data-term wave of another workgroup runs up to 25 % slower (measured).  (FOTG_VR_LEVELPIPE = 1 + 16 * dbg; dbg & 8: no)
+    p.excl = (p.lp_nwg <= 256 && !((c->tune.vr_levelpipe >> 4) & 8)) ? 72 * 1024 : 0;
+  }
+  return p;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: opt kernel fn in to lds bytes once per (kernel,
+// device).  Contexts / pipes driven from different host threads share the cache.
+static std::mutex g_lds_mu;
+static std::map<std::pair<const void *, int>, int> g_lds_set;
+template <typename... A>
+static int opt_in_lds(void (*fn)(A...), int lds)
 {
   std::lock_guard<std::mutex> lock(g_lds_mu);
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) { (void)hipGetLastError(); dev = 0; }
-  if (lds <= set[dev]) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { (void)hipGetLastError(); return false; }
-  set[dev] = lds;
-  return true;
+  HIPCHK(hipGetDevice(&dev));
+  int &have = g_lds_set[{reinterpret_cast<const void *>(fn), dev}];
+  if (lds <= have) return FOTG_OK;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  have = lds;
+  return FOTG_OK;
 }
 
-static std::atomic<long> g_fused_cglobal_launches{0};   // fotg_debug_counter("fused_cglobal"): fused per-level launches with the system in global memory
-static std::atomic<long> g_pipe_launches{0};            // fotg_debug_counter("sor_pipe"): vr_sor_pipe_kernel launches
-static bool launch_sor_pipe(int n, float omega, hipStream_t s, const VrArgs &b)
-{
-  constexpr int P = 8, U = 32;
-  const int lds = 128 + (b.S + 2) * b.RPD * (int)sizeof(float2);
-  static int lds_set[32] = {0};
-  if (!ensure_dyn_lds(reinterpret_cast<const void *>(&vr_sor_pipe_kernel<P, U>), lds, lds_set)) return false;
-  vr_sor_pipe_kernel<P, U><<<n, 1024, lds, s>>>(b, omega);          // all 16 waves copy D in and out
-  ++g_pipe_launches;
-  return true;
-}
+// launches since the library was loaded: fotg_debug_counter(name) (tests assert that a kernel really ran).  fused_cglobal: fused launches
+// with the system in global memory; sor_tall: sor_coupled calls (not launches) run by vr_sor_tall_kernel
+enum LaunchCount { CNT_SOR_STREAM, CNT_SOR_PIPE, CNT_FUSED_CGLOBAL, CNT_SOR_TILES, CNT_SOR_TALL, CNT_LEVEL_PIPE, CNT_N };
+static const char *const g_count_name[CNT_N] = {"sor_stream", "sor_pipe", "fused_cglobal", "sor_tiles", "sor_tall", "level_pipe"};
+static std::atomic<long> g_count[CNT_N];
 
-static std::atomic<long> g_tile_launches{0};        // fotg_debug_counter("sor_tiles")
-static std::atomic<long> g_tall_launches{0};        // fotg_debug_counter("sor_tall")
-static std::atomic<long> g_levelpipe_launches{0};   // fotg_debug_counter("level_pipe")
 #ifndef FOTG_TILE_P
 #define FOTG_TILE_P 8                    // prefetch depth (diagonals) of the tile solver
 #endif
-static int a_level(const fotg_ctx *c, const VrArgs &a) { for (int l = c->p.sc_l; l <= c->p.sc_f; ++l) if (c->vra[l].w == a.w && c->vra[l].h == a.h) return l; return c->p.sc_l; }
-static std::atomic<long> g_stream_launches{0};      // fotg_debug_counter("sor_stream"): tests assert the kernel really ran
-// streaming solver (vr_sor_stream_kernel): diagonals travel through LDS rings, two rows per lane.
-template <int RD, int RCW, bool FMA = false>
-static bool launch_sor_stream_k(const VrArgs &b, int n, float omega, hipStream_t s)
+// the tile pipeline's arguments for n pairs of level l (vr_sor_tile_kernel, vr_level_pipe_kernel)
+static TileArgs tile_args(const fotg_ctx *c, int l, int n)
 {
-  constexpr int M = FOTG_SYNC_M, U = 32;
-  using GEO = StreamGeom<RD, RCW>;
-  if (b.RP < 64 || b.RP + 1 > RCW || b.RPD > RD || (b.RPD & 1) || b.S < 2 * U) return false;
-  if (b.nsweeps > 3 || b.h + 2 > b.RPD) return false;
-  const int DS = ((M + 2 + M - 1) / M) * M;
-  const int omax = b.nsweeps > 0 ? (b.nsweeps - 1) * DS : 0;
-  const int RDN = M * (GEO::LI + omax / M + 1 + 1), RCN = RDN - M;
-  const int lds = RCN * GEO::CSLOT + RDN * GEO::DB + GEO::DB;
-  if (lds > 160 * 1024) return false;
-  static int lds_set[32] = {0};
-  if (!ensure_dyn_lds(reinterpret_cast<const void *>(&vr_sor_stream_kernel<RD, RCW, M, U, FMA>), lds, lds_set)) return false;
-  vr_sor_stream_kernel<RD, RCW, M, U, FMA><<<n, 1024, lds, s>>>(b, omega);
-  ++g_stream_launches;
-  return true;
+  const VrArgs &a = c->vra[l];
+  return {c->vrX[l], c->x_pair_stride[l], (long)(a.S + 1 + FOTG_TILE_DUMP) * c->x_rt[l], c->x_rt[l], (a.h + FOTG_TILE_ROWS - 1) / FOTG_TILE_ROWS, n,
+          c->tileSync, c->tile_nbs, c->tileSync + c->sync_total, c->stall_dev};
 }
 
-// Levels of 65..96 rows (1080p level 4: 68).  Two geometries: <= 69 rows and <= 97 rows per diagonal.
-// tune.vr_stream = 0 (FOTG_VR_STREAM=0 at context creation; tests): the resident-D kernel instead.
-static bool launch_sor_stream(const fotg_ctx *c, const VrArgs &b, int n, float omega, hipStream_t s)
+template <int K, int P, bool POINT = false>
+static void launch_sor_wave(const VrArgs &a, int n, int sweeps, float omega, hipStream_t s)
 {
-  if (!c->tune.vr_stream) return false;
-  if (c->p.fast_math) return launch_sor_stream_k<72, 70, true>(b, n, omega, s) || launch_sor_stream_k<100, 98, true>(b, n, omega, s);
-  return launch_sor_stream_k<72, 70>(b, n, omega, s) || launch_sor_stream_k<100, 98>(b, n, omega, s);
+  constexpr int U = POINT ? (K <= 4 ? 4 : 1) : (K <= 2) ? (P >= 8 ? 64 : 8 * P) : (K <= 4 ? 4 * P : P);     // steps per loop trip
+  vr_sor_kernel<K, P, U, POINT><<<n, 64, 0, s>>>(a, sweeps, omega);
 }
 
-// sweep-pipelined LDS solver when it applies: <= 4 sweeps (one wave each per band)
-static bool dispatch_sor_pipe(const fotg_ctx *c, const VrArgs &a, int n, int sweeps, float omega, hipStream_t s)
+// one sor_coupled call of level l as planned; zeroed: the launch in front has cleared the tile pipeline's sync words
+template <bool FM>
+static int run_sor(fotg_ctx *c, int l, int n, const SorPlan &q, bool zeroed, hipStream_t s)
 {
-#ifdef FOTG_DEBUG
-  if (const char *e = getenv("FOTG_DEBUG_SWEEPS")) sweeps = atoi(e);                    // timing experiments only (wrong results)
-#endif
-  const int lds = 128 + (a.S + 2) * a.RPD * (int)sizeof(float2);
-  if (sweeps < 1 || sweeps > 4 || a.S < 24) return false;
-  VrArgs b = a;
-  b.nsweeps = sweeps;
-#ifdef FOTG_DEBUG
-  if (getenv("FOTG_DEBUG_NOSOR")) b.nsweeps = 0;                // timing experiments only
-#endif
-  set_bands(b, sweeps);
-  if (b.band_mode != 3) return false;
-  if (launch_sor_stream(c, b, n, omega, s)) return true;        // 65..96 rows, any width: diagonals stream through LDS rings
-  if (lds > 150 * 1024) return false;                           // the kernel below keeps the whole (du,dv) in LDS
-  return launch_sor_pipe(n, omega, s, b);
-}
-
-static int fused_lds_bytes(const VrArgs &b, bool with_c)
-{
-  return 128 + (b.S + 2) * b.RPD * (int)sizeof(float2) + ((b.w * b.h + 3) / 4) * 16 + (with_c ? (b.SC * b.RP + 1) * 32 : 0);
-}
-
-template <int NOC, bool CL = false, bool RES = false, int NT = 512, bool FM = false>
-static bool launch_inner_fused(const VrArgs &b, int n, int inner, float qa, float hd, float hg, float omega, float *flow, long fs, hipStream_t s,
-                               const float *I0, const float *I1, long img_stride, int tw, int pad)
-{
-  constexpr int P = 8, U = 32;
-  const int lds = fused_lds_bytes(b, CL);
-  static int lds_set[32] = {0};
-  if (!ensure_dyn_lds(reinterpret_cast<const void *>(&vr_inner_fused_kernel<NOC, P, U, CL, RES, NT, FM>), lds, lds_set)) return false;
-  vr_inner_fused_kernel<NOC, P, U, CL, RES, NT, FM><<<n, NT, lds, s>>>(b, inner, qa, hd, hg, omega, flow, fs, I0, I1, img_stride, tw, pad);
-  return true;
-}
-
-// whole fixed-point loop in one launch when (du,dv) + the smoothness plane fit in LDS, sweeps <= 4 and the level has <= 64 rows
-template <int NOC>
-static bool dispatch_inner_fused(const fotg_ctx *c, const VrArgs &a, int n, int sweeps, int inner, float qa, float hd, float hg, float omega, float *flow,
-                                 long fs, hipStream_t s, const float *I0, const float *I1, long img_stride, int tw, int pad, int taps)
-{
-  // (fast_math: the data term in the tolerance mode's arithmetic, varref_dataterm.inc.h)
-#define FOTG_FUSED(...) (c->p.fast_math ? launch_inner_fused<__VA_ARGS__, true>(b, n, inner, qa, hd, hg, omega, flow, fs, s, I0, I1, img_stride, tw, pad) \
-                                        : launch_inner_fused<__VA_ARGS__, false>(b, n, inner, qa, hd, hg, omega, flow, fs, s, I0, I1, img_stride, tw, pad))
-  const int lds = fused_lds_bytes(a, false);
-  // one workgroup does the per-pixel phases of its pair: only worth it for small levels (measured: 60x34 yes, 120x68 no)
-  // (red-black has no dependency chain: its half-sweeps use all the workgroup's threads, and one launch per level beats
-  // 2 + inner (1 + 2 sweeps) launches at any level whose (du,dv) and smoothness plane fit in LDS -- 1080p level 4 included)
-  const bool rb = c->p.sor_mode == FOTG_SOR_REDBLACK;
-  if (sweeps < 1 || sweeps > 4 || inner < 1 || lds > 156 * 1024 || a.S < 24 || (a.w * a.h > 3000 && !rb)) return false;
-  VrArgs b = a;
-  b.taps = taps;
-  b.nsweeps = sweeps;
-  b.redblack = rb;
-#ifdef FOTG_DEBUG
-  if (getenv("FOTG_DEBUG_NOSOR")) b.nsweeps = 0;                // timing experiments only
-#endif
-  set_bands(b, sweeps);
-  if (b.band_mode != 3 || b.nbands > 1) return false;           // the fused kernel's barrier-stepped waves assume a single band (<= 64 rows)
-  // system cells in LDS as well when they fit
-  if (fused_lds_bytes(a, true) <= 160 * 1024) {
-    // gray levels of <= 4 pixels per thread also keep their per-pixel inputs in registers over the loop
-    if constexpr (NOC == 1) {
-      // (levels of more than 1024 pixels: 1024 threads, two pixels each -- 4 waves per SIMD hide the latencies of the per-pixel phases)
-      if (a.w * a.h > 1024 && a.w * a.h <= 2048 && FOTG_FUSED(1, true, true, 1024)) return true;
-      if (a.w * a.h <= 4 * 512 && FOTG_FUSED(1, true, true, 512)) return true;
-    }
-    if (FOTG_FUSED(NOC, true, false, 512)) return true;
-  }
-  // wide, short levels whose skewed system (w + h) x h x 32 B does not fit beside (du,dv) and the smoothness plane -- e.g. 100 x 30: 133 KB --
-  // keep it in global memory (fotg_debug_counter("fused_cglobal") counts these launches)
-  if (!FOTG_FUSED(NOC, false, false, 512)) return false;
-  ++g_fused_cglobal_launches;
-  return true;
-#undef FOTG_FUSED
-}
-
-// FOTG_SOR_POINT (sor_coupled_slow_but_readable, a compatibility mode): the single-wave wavefront solver with the point update
-static void dispatch_sor_point(const VrArgs &a, int n, int sweeps, float omega, hipStream_t s)
-{
-  if (a.h > 1024) {                  // more rows than 64 lanes x 16: a sweep per launch, rows looped (vr_sor_tall_kernel)
-    for (int k = 0; k < sweeps; ++k) vr_sor_tall_kernel<true><<<n, 1024, 0, s>>>(a, omega);
-    ++g_tall_launches;
-    return;
-  }
-  switch (a.K) {
-#define PT(K_) case K_: vr_sor_kernel<K_, 1, (K_ <= 4 ? 4 : 1), true><<<n, 64, 0, s>>>(a, sweeps, omega); break
-    PT(1); PT(2); PT(3); PT(4); PT(6); PT(8); PT(12);
-    default: vr_sor_kernel<16, 1, 1, true><<<n, 64, 0, s>>>(a, sweeps, omega); break;
-#undef PT
-  }
-}
-
-static void dispatch_sor(const fotg_ctx *c, const VrArgs &a, int n, int sweeps, float omega, hipStream_t s, bool sync_zeroed = false)
-{
-  const int path = c->tune.vr_path;    // 0 = automatic, 1 = single-wave global-memory solver only, 2 = no fused inner loop (tests)
-  if (path != 1 && dispatch_sor_pipe(c, a, n, sweeps, omega, s)) return;
-  // FOTG_VR_PATH=1 -- tests, and the recompute of a stalled tile pipeline -- uses no inter-workgroup waits anywhere: levels of more than
-  // 1024 rows take the one-workgroup-per-pair wavefront (a sweep per launch), shorter ones the single-wave kernel below
-  if (path == 1 && a.h > 1024) {
-    for (int k = 0; k < sweeps; ++k) vr_sor_tall_kernel<false><<<n, 1024, 0, s>>>(a, omega);
-    ++g_tall_launches;
-    return;
-  }
-  // levels too tall for the LDS solvers: tiles = (sweep, band of 64 rows), one workgroup each, pipelined through global memory
-  // (varref_tiles.hip.h)
-  if (path != 1 && c->vrX[a_level(c, a)] && c->tileSync) {
-    const int l = a_level(c, a);
-    TileArgs g;
-    g.X = c->vrX[l] + (size_t)(a.C - c->vrC[l]) / a.c_pair_stride * c->x_pair_stride[l];      // (views: same pair offset as C)
-    g.x_pair_stride = c->x_pair_stride[l];
-    g.x_buf_stride = (long)(a.S + 1 + FOTG_TILE_DUMP) * c->x_rt[l];
-    g.RT = c->x_rt[l];
-    g.NB = (a.h + FOTG_TILE_ROWS - 1) / FOTG_TILE_ROWS;
-    g.npairs = n;
-    g.sync = c->tileSync;
-    g.NBS = c->tile_nbs;
-    g.timeouts = g.sync + c->sync_total;
-    g.stall_flag = c->stall_dev;
+  const VrArgs &a = c->vra[l];
+  const int sweeps = c->p.tv_solverit;
+  const float omega = c->p.tv_sor;
+  int st = FOTG_OK;
+  switch (q.kind) {
+    case SOR_NONE: return FOTG_OK;
+    case SOR_STREAM70:
+      if ((st = opt_in_lds(vr_sor_stream_kernel<72, 70, FOTG_SYNC_M, kVrU, FM>, q.lds))) return st;
+      vr_sor_stream_kernel<72, 70, FOTG_SYNC_M, kVrU, FM><<<n, 1024, q.lds, s>>>(with_bands(a, q.nsweeps, q.nbands), omega);
+      ++g_count[CNT_SOR_STREAM];
+      break;
+    case SOR_STREAM98:
+      if ((st = opt_in_lds(vr_sor_stream_kernel<100, 98, FOTG_SYNC_M, kVrU, FM>, q.lds))) return st;
+      vr_sor_stream_kernel<100, 98, FOTG_SYNC_M, kVrU, FM><<<n, 1024, q.lds, s>>>(with_bands(a, q.nsweeps, q.nbands), omega);
+      ++g_count[CNT_SOR_STREAM];
+      break;
+    case SOR_PIPE:
+      if ((st = opt_in_lds(vr_sor_pipe_kernel<kVrP, kVrU>, q.lds))) return st;
+      vr_sor_pipe_kernel<kVrP, kVrU><<<n, 1024, q.lds, s>>>(with_bands(a, q.nsweeps, q.nbands), omega);          // all 16 waves copy D in and out
+      ++g_count[CNT_SOR_PIPE];
+      break;
+    case SOR_TILES: {
+      TileArgs g = tile_args(c, l, n);
 #ifdef FOTG_TILE_STATS
-    if (!c->stamps) { if (hipMalloc((void **)&c->stamps, 4096 * 32 * 8) != hipSuccess) return; }
-    (void)hipMemsetAsync(c->stamps, 0, 4096 * 32 * 8, s);
-    g.stats = (long long *)c->stamps;
+      if (!c->stamps && hipMalloc((void **)&c->stamps, 4096 * 32 * 8) != hipSuccess) return FOTG_ERR_HIP;
+      (void)hipMemsetAsync(c->stamps, 0, 4096 * 32 * 8, s);
+      g.stats = (long long *)c->stamps;
 #endif
-    // the sweeps are sequential passes over the same system, every launch starts from and ends in the level's D: more than four
-    // sweeps = consecutive launches of at most four (one wave per sweep and band, X buffers for four), the same bits
-    for (int done = 0; done < sweeps; done += 4) {
-      const int sw = sweeps - done < 4 ? sweeps - done : 4;
-      // (the data-term launch in front of the call has cleared the words already when the caller arranged that: VrArgs::zsync)
-      if (!(sync_zeroed && done == 0)) (void)hipMemsetAsync(g.sync, 0, (size_t)tile_sync_words(n, c->tile_nbs) * sizeof(int), s);
-      if (c->p.fast_math) vr_sor_tile_kernel<FOTG_TILE_P, true><<<n * g.NB * sw, FOTG_TILE_THREADS, 0, s>>>(a, g, sw, omega);
-      else vr_sor_tile_kernel<FOTG_TILE_P><<<n * g.NB * sw, FOTG_TILE_THREADS, 0, s>>>(a, g, sw, omega);
-      ++g_tile_launches;
+      // the sweeps are sequential passes over the same system, every launch starts from and ends in the level's D: more than four
+      // sweeps = consecutive launches of at most four (one wave per sweep and band, X buffers for four), the same bits
+      for (int done = 0; done < sweeps; done += 4) {
+        const int sw = sweeps - done < 4 ? sweeps - done : 4;
+        if (!(zeroed && done == 0)) (void)hipMemsetAsync(g.sync, 0, (size_t)tile_sync_words(n, c->tile_nbs) * sizeof(int), s);
+        vr_sor_tile_kernel<FOTG_TILE_P, FM><<<n * g.NB * sw, FOTG_TILE_THREADS, 0, s>>>(a, g, sw, omega);
+        ++g_count[CNT_SOR_TILES];
+      }
+      break;
     }
-    return;
+    case SOR_TALL: for (int k = 0; k < sweeps; ++k) vr_sor_tall_kernel<false><<<n, 1024, 0, s>>>(a, omega); ++g_count[CNT_SOR_TALL]; break;
+    case SOR_POINT_TALL: for (int k = 0; k < sweeps; ++k) vr_sor_tall_kernel<true><<<n, 1024, 0, s>>>(a, omega); ++g_count[CNT_SOR_TALL]; break;
+    case SOR_WAVE:
+      switch (a.K * 100 + q.P) {
+#define WAVE(K_, P_) case K_ * 100 + P_: launch_sor_wave<K_, P_>(a, n, sweeps, omega, s); break
+        WAVE(1, 16); WAVE(1, 8); WAVE(1, 4); WAVE(1, 2); WAVE(1, 1); WAVE(2, 8); WAVE(2, 4); WAVE(2, 2); WAVE(2, 1);
+        WAVE(3, 4); WAVE(3, 2); WAVE(3, 1); WAVE(4, 4); WAVE(4, 2); WAVE(4, 1); WAVE(6, 1); WAVE(8, 1); WAVE(12, 1);
+        default: launch_sor_wave<16, 1>(a, n, sweeps, omega, s); break;
+#undef WAVE
+      }
+      break;
+    case SOR_POINT:
+      switch (a.K) {
+#define PT(K_) case K_: launch_sor_wave<K_, 1, true>(a, n, sweeps, omega, s); break
+        PT(1); PT(2); PT(3); PT(4); PT(6); PT(8); PT(12);
+        default: launch_sor_wave<16, 1, true>(a, n, sweeps, omega, s); break;
+#undef PT
+      }
+      break;
+    case SOR_REDBLACK:
+      // one launch per half-sweep: every cell of the even, then of the odd diagonals, the whole batch at once
+      for (int sw = 0; sw < sweeps; ++sw)
+        for (int col = 0; col < 2; ++col) {
+          const int nd = (a.S - col + 1) / 2;
+          vr_rb_halfsweep_kernel<<<dim3((nd * a.RP + 255) / 256, n), 256, 0, s>>>(a, col, omega);
+        }
+      break;
   }
-  // prefetch depth: as deep as the register budget of K rows per lane allows, and 2P+2 <= S (ring never
-  // runs ahead into rows the current sweep has not rewritten yet)
-  const int cap = (a.S - 2) / 2;
-  auto pick = [&](int pmax) { int p = pmax; while (p > 1 && p > cap) p >>= 1; return p; };
-  switch (a.K) {
-    case 1: switch (pick(16)) { case 16: launch_sor<1, 16>(a, n, sweeps, omega, s); break; case 8: launch_sor<1, 8>(a, n, sweeps, omega, s); break; case 4: launch_sor<1, 4>(a, n, sweeps, omega, s); break;
-                               case 2: launch_sor<1, 2>(a, n, sweeps, omega, s); break; default: launch_sor<1, 1>(a, n, sweeps, omega, s); } break;
-    case 2: switch (pick(8)) { case 8: launch_sor<2, 8>(a, n, sweeps, omega, s); break; case 4: launch_sor<2, 4>(a, n, sweeps, omega, s); break;
-                               case 2: launch_sor<2, 2>(a, n, sweeps, omega, s); break; default: launch_sor<2, 1>(a, n, sweeps, omega, s); } break;
-    case 3: switch (pick(4)) { case 4: launch_sor<3, 4>(a, n, sweeps, omega, s); break; case 2: launch_sor<3, 2>(a, n, sweeps, omega, s); break;
-                               default: launch_sor<3, 1>(a, n, sweeps, omega, s); } break;
-    case 4: switch (pick(4)) { case 4: launch_sor<4, 4>(a, n, sweeps, omega, s); break; case 2: launch_sor<4, 2>(a, n, sweeps, omega, s); break;
-                               default: launch_sor<4, 1>(a, n, sweeps, omega, s); } break;
-    case 6: launch_sor<6, 1>(a, n, sweeps, omega, s); break;
-    case 8: launch_sor<8, 1>(a, n, sweeps, omega, s); break;
-    case 12: launch_sor<12, 1>(a, n, sweeps, omega, s); break;
-    default: launch_sor<16, 1>(a, n, sweeps, omega, s); break;
-  }
+  LAUNCHCHK();
+  return FOTG_OK;
 }
 
-template <int NOC>
+template <int NOC, bool CL, bool RES, int NT, bool FM>
+static int launch_fused(const VrArgs &b, int lds, int n, hipStream_t s, int inner, float qa, float hd, float hg, float omega, float *flow, long fs,
+                        const float *I0, const float *I1, long img_stride, int tw, int pad)
+{
+  int st = opt_in_lds(vr_inner_fused_kernel<NOC, kVrP, kVrU, CL, RES, NT, FM>, lds);
+  if (st) return st;
+  vr_inner_fused_kernel<NOC, kVrP, kVrU, CL, RES, NT, FM><<<n, NT, lds, s>>>(b, inner, qa, hd, hg, omega, flow, fs, I0, I1, img_stride, tw, pad);
+  return FOTG_OK;
+}
+
+// FM: fotg_params::fast_math -- the data term in the tolerance mode's arithmetic (varref_dataterm.inc.h), the solvers' cell update with
+// fused multiply-adds
+template <int NOC, bool FM>
 static int varref_impl(fotg_ctx *c, int l, int n, const float *I0, const float *I1, long img_stride, float *flow, hipStream_t s)
 {
   const LevelGeom &g = c->geom[l];
@@ -1042,52 +1077,37 @@ static int varref_impl(fotg_ctx *c, int l, int n, const float *I0, const float *
   const float half_gamma_over3 = c->p.tv_gamma * 0.5f / 3.0f;
   const float half_delta_over3 = c->p.tv_delta * 0.5f / 3.0f;
   const int inner = c->p.tv_innerit * (l + 1);
-  // small levels: the whole level (set-up stages, fixed-point loop, final w + d) in one launch, one workgroup per pair
-  if (c->p.sor_mode != FOTG_SOR_POINT && c->p.tv_solverit > 0 && c->tune.vr_path == 0 &&
-      dispatch_inner_fused<NOC>(c, a, n, c->p.tv_solverit, inner, quarter_alpha, half_delta_over3, half_gamma_over3, c->p.tv_sor, flow, fs, s,
-                                I0, I1, img_stride, g.tw, c->ps, c->taps ? 1 : 0)) {
+  const VrPlan p = plan_level(c, l, n);
+  int st = FOTG_OK;
+  if (p.fused != FUSED_NONE) {
+    VrArgs b = with_bands(a, p.nsweeps, 1);
+    b.taps = c->taps ? 1 : 0;
+    b.redblack = c->p.sor_mode == FOTG_SOR_REDBLACK;
+    const auto fused = [&](auto launch) {       // (launch: an instance of launch_fused)
+      return launch(b, p.lds, n, s, inner, quarter_alpha, half_delta_over3, half_gamma_over3, c->p.tv_sor, flow, fs, I0, I1, img_stride, g.tw, c->ps);
+    };
+    switch (p.fused) {
+      case FUSED_RES1024: if constexpr (NOC == 1) st = fused(launch_fused<1, true, true, 1024, FM>); break;
+      case FUSED_RES: if constexpr (NOC == 1) st = fused(launch_fused<1, true, true, 512, FM>); break;
+      case FUSED_CL: st = fused(launch_fused<NOC, true, false, 512, FM>); break;
+      default: st = fused(launch_fused<NOC, false, false, 512, FM>); ++g_count[CNT_FUSED_CGLOBAL]; break;
+    }
+    if (st) return st;
     LAUNCHCHK();
     return FOTG_OK;
   }
-  // levels that go through the tile pipeline: the launch in front of every sor_coupled call (data term; set-up with the first data
-  // term) clears the pipeline's sync words
   VrArgs az = a;
-  const bool tiles = c->p.sor_mode == FOTG_SOR_LEXICOGRAPHIC && c->vrX[l] && c->tileSync && c->p.tv_solverit > 0;
-  if (tiles) { az.zsync = c->tileSync; az.zsync_n = (int)tile_sync_words(n, c->tile_nbs); }
-  // FOTG_VR_LEVELPIPE=1: the level's whole fixed-point loop as ONE pipeline launch behind the set-up launch (varref_levelpipe.hip.h).
-  // At least two sweeps per call (what keeps a band's last sweep behind the data term of its neighbours), at most four (X buffers).
-  const int ntr = (g.h + FOTG_LP_TH - 1) / FOTG_LP_TH;
-  const bool levelpipe = tiles && c->tune.vr_levelpipe && n <= c->tune.lp_max_pairs && c->tune.vr_path == 0 && c->tune.vr_first_data && inner >= 1 && inner <= FOTG_LP_KMAX &&
-                         c->p.tv_solverit >= 2 && c->p.tv_solverit <= 4 && ntr <= c->lp_ntr &&
-                         lp_tile_words(n, c->tile_nbs) + lp_data_words(n, ntr) <= c->sync_total;
-  if (levelpipe) { az.zsync_n = (int)(lp_tile_words(n, c->tile_nbs) + lp_data_words(n, ntr)); }
-  // warp + first + second derivatives in one tiled launch, which also zeroes (du,dv) (refine_variational.cpp:185-186) and builds the
-  // system of the first inner iteration (unless tune.vr_first_data = 0: a data-term launch of its own)
-  const bool merged_first = c->tune.vr_first_data && inner > 0;
+  if (p.zsync_n) { az.zsync = c->tileSync; az.zsync_n = p.zsync_n; }
   {
     dim3 gs_(((g.w + 31) / 32) * ((g.h + 7) / 8), n);
     // (1..7 pairs, a launch that spans the chip: XCD-banded tiles like the LK launches; FOTG_LK_BANDED=0: plain order)
     if ((n & 7) != 0 && gs_.x >= 256 && c->tune.lk_banded) { az.nwg = (int)gs_.x; gs_.x = (gs_.x + 7) & ~7u; }
-    if (c->p.fast_math)
-      vr_setup_kernel<NOC, 2, true><<<gs_, 256, 0, s>>>(az, I0, I1, img_stride, g.tw, c->ps, flow, fs, 1, merged_first ? 1 : 0, quarter_alpha, half_delta_over3, half_gamma_over3);
-    else
-      vr_setup_kernel<NOC><<<gs_, 256, 0, s>>>(az, I0, I1, img_stride, g.tw, c->ps, flow, fs, 1, merged_first ? 1 : 0, quarter_alpha, half_delta_over3, half_gamma_over3);
+    vr_setup_kernel<NOC, 2, FM><<<gs_, 256, 0, s>>>(az, I0, I1, img_stride, g.tw, c->ps, flow, fs, 1, p.merged_first ? 1 : 0, quarter_alpha, half_delta_over3, half_gamma_over3);
     LAUNCHCHK();
   }
-  if (levelpipe) {
-    TileArgs tg;
-    tg.X = c->vrX[l] + (size_t)(a.C - c->vrC[l]) / a.c_pair_stride * c->x_pair_stride[l];
-    tg.x_pair_stride = c->x_pair_stride[l];
-    tg.x_buf_stride = (long)(a.S + 1 + FOTG_TILE_DUMP) * c->x_rt[l];
-    tg.RT = c->x_rt[l];
-    tg.NB = (a.h + FOTG_TILE_ROWS - 1) / FOTG_TILE_ROWS;
-    tg.npairs = n;
-    tg.sync = c->tileSync;
-    tg.NBS = c->tile_nbs;
-    tg.timeouts = tg.sync + c->sync_total;
-    tg.stall_flag = c->stall_dev;
+  if (p.levelpipe) {
     LevelPipeArgs q;
-    q.K = inner; q.ntr = ntr; q.tiles_x = (g.w + FOTG_TW - 1) / FOTG_TW;
+    q.K = inner; q.ntr = (g.h + FOTG_LP_TH - 1) / FOTG_LP_TH; q.tiles_x = (g.w + FOTG_TW - 1) / FOTG_TW;
     q.dprog = c->tileSync + lp_tile_words(n, c->tile_nbs);
     q.quarter_alpha = quarter_alpha; q.half_delta_over3 = half_delta_over3; q.half_gamma_over3 = half_gamma_over3;
     q.dbg = c->tune.vr_levelpipe >> 4;       // (FOTG_VR_LEVELPIPE = 1 + 16 * dbg)
@@ -1097,53 +1117,69 @@ static int varref_impl(fotg_ctx *c, int l, int n, const float *I0, const float *
       (void)hipMemsetAsync(c->stamps, 0, 8 * 8 * 8192, s);
       q.stamps = (long long *)c->stamps;
     }
-    const int sw = c->p.tv_solverit;
-    const unsigned nwg = (unsigned)n * (unsigned)(inner * tg.NB * sw + (inner - 1) * ntr * FOTG_LP_DW);
-    // a launch that fits the chip with one workgroup per CU asks for enough LDS to get exactly that: a solver wave that shares its
-    // SIMD with a data-term wave of another workgroup runs up to 25 % slower (measured)
-    const int excl = (nwg <= 256 && !(q.dbg & 8)) ? 72 * 1024 : 0;
-    if (c->p.fast_math) {
-      static int lds_set[32] = {0};
-      if (excl && !ensure_dyn_lds(reinterpret_cast<const void *>(&vr_level_pipe_kernel<NOC, FOTG_TILE_P, true>), excl, lds_set)) return FOTG_ERR_HIP;
-      vr_level_pipe_kernel<NOC, FOTG_TILE_P, true><<<nwg, 256, excl, s>>>(a, tg, q, sw, c->p.tv_sor);
-    } else {
-      static int lds_set[32] = {0};
-      if (excl && !ensure_dyn_lds(reinterpret_cast<const void *>(&vr_level_pipe_kernel<NOC, FOTG_TILE_P, false>), excl, lds_set)) return FOTG_ERR_HIP;
-      vr_level_pipe_kernel<NOC, FOTG_TILE_P, false><<<nwg, 256, excl, s>>>(a, tg, q, sw, c->p.tv_sor);
-    }
+    if (p.excl && (st = opt_in_lds(vr_level_pipe_kernel<NOC, FOTG_TILE_P, FM>, p.excl))) return st;
+    vr_level_pipe_kernel<NOC, FOTG_TILE_P, FM><<<p.lp_nwg, 256, p.excl, s>>>(a, tile_args(c, l, n), q, c->p.tv_solverit, c->p.tv_sor);
     LAUNCHCHK();
-    ++g_levelpipe_launches;
+    ++g_count[CNT_LEVEL_PIPE];
     vr_finish_kernel<<<grid, block, 0, s>>>(a, flow, fs);
     LAUNCHCHK();
     return FOTG_OK;
   }
   for (int it = 0; it < inner; ++it) {
-    if (!(it == 0 && merged_first)) {
-      if (c->p.fast_math) vr_data_kernel<NOC, true><<<dim3(((g.w + FOTG_TW - 1) / FOTG_TW) * ((g.h + FOTG_TH - 1) / FOTG_TH), n), 256, 0, s>>>(az, quarter_alpha, half_delta_over3, half_gamma_over3);
-      else vr_data_kernel<NOC><<<dim3(((g.w + FOTG_TW - 1) / FOTG_TW) * ((g.h + FOTG_TH - 1) / FOTG_TH), n), 256, 0, s>>>(az, quarter_alpha, half_delta_over3, half_gamma_over3);
+    if (!(it == 0 && p.merged_first)) {
+      vr_data_kernel<NOC, FM><<<dim3(((g.w + FOTG_TW - 1) / FOTG_TW) * ((g.h + FOTG_TH - 1) / FOTG_TH), n), 256, 0, s>>>(az, quarter_alpha, half_delta_over3, half_gamma_over3);
       LAUNCHCHK();
     }
-    if (c->p.tv_solverit > 0) {
-      if (c->p.sor_mode == FOTG_SOR_REDBLACK) {
-        // one launch per half-sweep: every cell of the even, then of the odd diagonals, the whole batch at once
-        for (int sw = 0; sw < c->p.tv_solverit; ++sw)
-          for (int col = 0; col < 2; ++col) {
-            const int nd = (a.S - col + 1) / 2;
-            vr_rb_halfsweep_kernel<<<dim3((nd * a.RP + 255) / 256, n), 256, 0, s>>>(a, col, c->p.tv_sor);
-          }
-      }
-      else if (c->p.sor_mode == FOTG_SOR_POINT) dispatch_sor_point(a, n, c->p.tv_solverit, c->p.tv_sor, s);
-      else dispatch_sor(c, a, n, c->p.tv_solverit, c->p.tv_sor, s, tiles);
-      LAUNCHCHK();
-    }
+    if ((st = run_sor<FM>(c, l, n, p.sor, p.zsync_n != 0, s))) return st;
   }
   vr_finish_kernel<<<grid, block, 0, s>>>(a, flow, fs);
   LAUNCHCHK();
   return FOTG_OK;
 }
 
+// stereo depth mode, RefLevelDE's fixed-point loop: everything after the set-up in one vr_de_inner_kernel launch; vr_de_sor_tall_kernel
+// (more rows than a workgroup has threads: a sweep per launch, rows looped); vr_de_sor_kernel <3, LDS, true> (a wave group per sweep),
+// <3, LDS>, <1, LDS> (a sweep per launch)
+enum DeKind { DE_INNER, DE_TALL, DE_SPLIT, DE_SW3, DE_SW1 };
+struct DePlan {
+  DeKind kind;
+  int threads;                          // one per row, whole waves
+  int lds_mode, lds;                    // LDS of vr_de_sor_kernel: 2 = du + the four coefficient planes, 1 = du alone, 0 = none; bytes
+};
+static DePlan plan_depth(const fotg_ctx *c, int l)
+{
+  const LevelGeom &g = c->geom[l];
+  DePlan p;
+  p.threads = ((g.h + 63) / 64) * 64;
+  const int du_bytes = g.st * g.h * (int)sizeof(float);
+  // du + the four coefficient planes in LDS when they fit in the CU's 160 KiB, else du alone, else global memory
+  p.lds_mode = 5 * du_bytes <= FOTG_LDS_MAX ? 2 : du_bytes <= 128 * 1024 ? 1 : 0;
+  p.lds = p.lds_mode == 2 ? 5 * du_bytes : p.lds_mode == 1 ? du_bytes : 0;
+  // the sweeps are sequential passes over du, so `k` single-sweep launches equal one k-sweep launch bit for bit; the operating points
+  // use 3.  Levels up to 8192 cells with three sweeps: everything after the set-up in one launch per level (FOTG_VR_PATH != 0 forces
+  // the launch-per-stage path; tests)
+  const bool split = c->p.tv_solverit == 3 && 3 * p.threads <= 1024;
+  if (split && p.lds_mode == 2 && c->tune.vr_path == 0) p.kind = DE_INNER;
+  else if (g.h > 1024) p.kind = DE_TALL;
+  else if (split && p.lds_mode) p.kind = DE_SPLIT;
+  else p.kind = c->p.tv_solverit == 3 ? DE_SW3 : DE_SW1;
+  return p;
+}
+
+template <int SW, bool SPLIT = false>
+static int launch_de_sor(const VrArgs &a, int n, const DePlan &p, float omega, int camlr, hipStream_t s)
+{
+  const int nt = SPLIT ? 3 * p.threads : p.threads;
+  int st = FOTG_OK;
+  switch (p.lds_mode) {
+    case 2: if (!(st = opt_in_lds(vr_de_sor_kernel<SW, 2, SPLIT>, p.lds))) vr_de_sor_kernel<SW, 2, SPLIT><<<n, nt, p.lds, s>>>(a, omega, camlr); break;
+    case 1: if (!(st = opt_in_lds(vr_de_sor_kernel<SW, 1, SPLIT>, p.lds))) vr_de_sor_kernel<SW, 1, SPLIT><<<n, nt, p.lds, s>>>(a, omega, camlr); break;
+    default: if constexpr (!SPLIT) vr_de_sor_kernel<SW, 0><<<n, nt, 0, s>>>(a, omega, camlr); break;      // (DE_SPLIT has LDS)
+  }
+  return st;
+}
+
 // stereo depth mode: RefLevelDE (kroeger/refine_variational.cpp:243-330), flow has one channel
-static bool g_de_lds_set[32];
 template <int NOC>
 static int varref_depth_impl(fotg_ctx *c, int l, int n, const float *I0, const float *I1, long img_stride, float *flow, hipStream_t s, int camlr)
 {
@@ -1155,70 +1191,35 @@ static int varref_depth_impl(fotg_ctx *c, int l, int n, const float *I0, const f
   const float half_gamma_over3 = c->p.tv_gamma * 0.5f / 3.0f;
   const float half_delta_over3 = c->p.tv_delta * 0.5f / 3.0f;
   const int inner = c->p.tv_innerit * (l + 1);
+  const int sweeps = c->p.tv_solverit;
+  const float omega = c->p.tv_sor;
+  const DePlan p = plan_depth(c, l);
+  int st = FOTG_OK;
   vr_setup_kernel<NOC, 1><<<dim3(((g.w + 31) / 32) * ((g.h + 7) / 8), n), 256, 0, s>>>(a, I0, I1, img_stride, g.tw, c->ps, flow, fs);
   LAUNCHCHK();
-  const int threads = ((g.h + 63) / 64) * 64;
-  const int du_bytes = g.st * g.h * (int)sizeof(float);
-  // levels up to 8192 cells with the operating points' three sweeps: everything after the set-up in one launch per level
-  // (FOTG_VR_PATH != 0 forces the launch-per-stage path below; tests)
-  if (5 * du_bytes <= 160 * 1024 && c->p.tv_solverit == 3 && 3 * threads <= 1024 && c->tune.vr_path == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    static bool set[32];
-    std::lock_guard<std::mutex> lock(g_lds_mu);
-    if (dev >= 0 && dev < 32 && !set[dev]) {
-      HIPCHK(hipFuncSetAttribute((const void *)vr_de_inner_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)vr_de_inner_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      set[dev] = true;
-    }
-    vr_de_inner_kernel<NOC><<<n, 1024, 5 * du_bytes, s>>>(a, inner, quarter_alpha, half_delta_over3, half_gamma_over3, c->p.tv_sor, camlr,
-                                                          flow, fs, threads, c->taps ? 1 : 0);
+  if (p.kind == DE_INNER) {
+    if ((st = opt_in_lds(vr_de_inner_kernel<NOC>, p.lds))) return st;
+    vr_de_inner_kernel<NOC><<<n, 1024, p.lds, s>>>(a, inner, quarter_alpha, half_delta_over3, half_gamma_over3, omega, camlr, flow, fs, p.threads, c->taps ? 1 : 0);
     LAUNCHCHK();
     return FOTG_OK;
   }
   vr_de_init_kernel<<<grid, block, 0, s>>>(a);
   LAUNCHCHK();
-  // du + the four coefficient planes in LDS when they fit in the CU's 160 KiB, else du alone, else global memory
-  const int lds = 5 * du_bytes <= 160 * 1024 ? 2 : du_bytes <= 128 * 1024 ? 1 : 0;
-  const int lds_bytes = lds == 2 ? 5 * du_bytes : lds == 1 ? du_bytes : 0;
-  if (lds_bytes > 64 * 1024) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(g_lds_mu);
-    if (dev >= 0 && dev < 32 && !g_de_lds_set[dev]) {
-      HIPCHK(hipFuncSetAttribute((const void *)vr_de_sor_kernel<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)vr_de_sor_kernel<3, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)vr_de_sor_kernel<3, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)vr_de_sor_kernel<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)vr_de_sor_kernel<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)vr_de_sor_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-      g_de_lds_set[dev] = true;
-    }
-  }
   for (int it = 0; it < inner; ++it) {
     vr_de_smooth_kernel<<<grid, block, 0, s>>>(a, quarter_alpha);
     LAUNCHCHK();
     vr_de_data_kernel<NOC><<<grid, block, 0, s>>>(a, half_delta_over3, half_gamma_over3);
     LAUNCHCHK();
-    // the sweeps are sequential passes over du, so `k` single-sweep launches equal one k-sweep launch bit for bit; the
-    // operating points use 3.  (With 0 sweeps the clamped update still runs: uu = min/max(wx + du, 0).)
-    if (g.h > 1024) {                                             // more rows than a workgroup has threads: one sweep per launch, rows looped
-      for (int k = 0; k < c->p.tv_solverit; ++k)
-        vr_de_sor_tall_kernel<<<n, 1024, 0, s>>>(a, c->p.tv_sor, camlr, k == c->p.tv_solverit - 1 ? 1 : 0);
-    } else if (c->p.tv_solverit == 3 && 3 * threads <= 1024 && lds) {     // one wave group per sweep
-      if (lds == 2) vr_de_sor_kernel<3, 2, true><<<n, 3 * threads, lds_bytes, s>>>(a, c->p.tv_sor, camlr);
-      else vr_de_sor_kernel<3, 1, true><<<n, 3 * threads, lds_bytes, s>>>(a, c->p.tv_sor, camlr);
-    } else if (c->p.tv_solverit == 3) {
-      if (lds == 2) vr_de_sor_kernel<3, 2><<<n, threads, lds_bytes, s>>>(a, c->p.tv_sor, camlr);
-      else if (lds == 1) vr_de_sor_kernel<3, 1><<<n, threads, lds_bytes, s>>>(a, c->p.tv_sor, camlr);
-      else vr_de_sor_kernel<3, 0><<<n, threads, 0, s>>>(a, c->p.tv_sor, camlr);
-    } else {
-      for (int k = 0; k < c->p.tv_solverit; ++k) {
-        if (lds == 2) vr_de_sor_kernel<1, 2><<<n, threads, lds_bytes, s>>>(a, c->p.tv_sor, camlr);
-        else if (lds == 1) vr_de_sor_kernel<1, 1><<<n, threads, lds_bytes, s>>>(a, c->p.tv_sor, camlr);
-        else vr_de_sor_kernel<1, 0><<<n, threads, 0, s>>>(a, c->p.tv_sor, camlr);
-      }
+    // (with 0 sweeps the clamped update still runs: uu = min/max(wx + du, 0))
+    switch (p.kind) {
+      case DE_TALL:
+        for (int k = 0; k < sweeps; ++k) vr_de_sor_tall_kernel<<<n, 1024, 0, s>>>(a, omega, camlr, k == sweeps - 1 ? 1 : 0);
+        break;
+      case DE_SPLIT: st = launch_de_sor<3, true>(a, n, p, omega, camlr, s); break;
+      case DE_SW3: st = launch_de_sor<3>(a, n, p, omega, camlr, s); break;
+      default: for (int k = 0; k < sweeps && !st; ++k) st = launch_de_sor<1>(a, n, p, omega, camlr, s); break;
     }
+    if (st) return st;
     LAUNCHCHK();
   }
   vr_de_finish_kernel<<<grid, block, 0, s>>>(a, flow, fs);
@@ -1235,8 +1236,9 @@ static int varref_dispatch(fotg_ctx *c, int l, int n, const float *I0, const flo
   if (c->p.depth)
     return c->noc == 1 ? varref_depth_impl<1>(c, l, n, I0, I1, pair_stride, flow, stream, camlr)
                        : varref_depth_impl<3>(c, l, n, I0, I1, pair_stride, flow, stream, camlr);
-  return c->noc == 1 ? varref_impl<1>(c, l, n, I0, I1, pair_stride, flow, stream)
-                     : varref_impl<3>(c, l, n, I0, I1, pair_stride, flow, stream);
+  if (c->p.fast_math)
+    return c->noc == 1 ? varref_impl<1, true>(c, l, n, I0, I1, pair_stride, flow, stream) : varref_impl<3, true>(c, l, n, I0, I1, pair_stride, flow, stream);
+  return c->noc == 1 ? varref_impl<1, false>(c, l, n, I0, I1, pair_stride, flow, stream) : varref_impl<3, false>(c, l, n, I0, I1, pair_stride, flow, stream);
 }
 
 extern "C" {
@@ -1248,9 +1250,8 @@ int fotg_bench_sor_call(fotg_ctx *c, int l, int n, void *stream)
   int st = check_level(c, l, n); if (st) return st;
   if (!c->vr || c->p.depth || !c->vrC[l] || c->p.tv_solverit < 1 || c->p.sor_mode != FOTG_SOR_LEXICOGRAPHIC) return FOTG_ERR_UNSUPPORTED;
   ON_DEVICE(c->device);
-  dispatch_sor(c, c->vra[l], n, c->p.tv_solverit, c->p.tv_sor, (hipStream_t)stream);
-  LAUNCHCHK();
-  return FOTG_OK;
+  const SorPlan q = plan_level(c, l, n).sor;
+  return c->p.fast_math ? run_sor<true>(c, l, n, q, false, (hipStream_t)stream) : run_sor<false>(c, l, n, q, false, (hipStream_t)stream);
 }
 
 int fotg_varref(fotg_ctx *c, int l, int n, const float *I0, const float *I1, long pair_stride, float *flow, void *stream)
@@ -1762,12 +1763,8 @@ int fotg_calc_sequence_u8(fotg_ctx *c, int n_frames, const unsigned char *frames
 
 long fotg_debug_counter(const char *name)
 {
-  if (name && !strcmp(name, "sor_stream")) return g_stream_launches;
-  if (name && !strcmp(name, "sor_pipe")) return g_pipe_launches;
-  if (name && !strcmp(name, "fused_cglobal")) return g_fused_cglobal_launches;
-  if (name && !strcmp(name, "sor_tiles")) return g_tile_launches;
-  if (name && !strcmp(name, "sor_tall")) return g_tall_launches;
-  if (name && !strcmp(name, "level_pipe")) return g_levelpipe_launches;
+  for (int k = 0; name && k < CNT_N; ++k)
+    if (!strcmp(name, g_count_name[k])) return g_count[k];
   return -1;
 }
 
