@@ -15,6 +15,9 @@ def __getattr__(name):
     if name in ("flow_to_color", "write_png", "color_wheel"):
         from . import color
         return getattr(color, name)
+    if name in ("fb_check", "upsample_crop_fb_check"):
+        from . import consistency
+        return getattr(consistency, name)
     if name == "FlowPipeline":
         from .pipeline import FlowPipeline
         return FlowPipeline

@@ -18,7 +18,8 @@ class FotgParams(C.Structure):
                 ("usetvref", C.c_int), ("tv_alpha", C.c_float), ("tv_gamma", C.c_float),
                 ("tv_delta", C.c_float), ("tv_innerit", C.c_int), ("tv_solverit", C.c_int),
                 ("tv_sor", C.c_float), ("sor_mode", C.c_int), ("costfct", C.c_int), ("normoutlier", C.c_float), ("usefbcon", C.c_int),
-                ("depth", C.c_int), ("u8_color", C.c_int), ("fast_math", C.c_int)]
+                ("depth", C.c_int), ("u8_color", C.c_int), ("fast_math", C.c_int),
+                ("bidir", C.c_int)]
 
 
 # every symbol include/fotg.h declares: (name, restype, argtypes)
@@ -35,6 +36,10 @@ SYMBOLS = [
     ("fotg_level_timings", C.c_int, [vp, C.c_int, f32p]),
     ("fotg_calc_sequence", C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
     ("fotg_calc_sequence_u8", C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+    ("fotg_calc_bidir", C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    ("fotg_calc_bidir_u8", C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    ("fotg_calc_sequence_bidir", C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    ("fotg_calc_sequence_bidir_u8", C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     ("fotg_pipe_create", C.c_int, [C.POINTER(FotgParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
     ("fotg_pipe_destroy", None, [vp]),
     ("fotg_pipe_submit", C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_long)]),
@@ -62,6 +67,8 @@ SYMBOLS = [
     ("fotg_gradient_magnitude_u8", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     ("fotg_flow_color", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
     ("fotg_upsample_crop_color", C.c_int, [vp, C.c_int, vp, C.c_float, vp, vp, vp]),
+    ("fotg_fb_check", C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_fb_check", C.c_int, [vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]),
     ("fotg_level_size", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_out_size", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_num_patches", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -17,6 +17,7 @@
 // atan2, computed as (float)atan2((double)y, (double)x) -- the reference calls glibc atan2f, which no GPU can match bit for bit.
 #pragma once
 #include "common.h"
+#include "flowsrc.hip.h"
 
 namespace fotg {
 
@@ -45,50 +46,6 @@ __device__ __forceinline__ bool fc_unknown(float u, float v)
 {
   return fabsf(u) > 1e9f || fabsf(v) > 1e9f || __builtin_isnan(u) || __builtin_isnan(v);   // 1e9 is exact in f32
 }
-
-// A dense flow: pixel p of the batch (linear, n x h x w) at flow[2 p].
-struct DenseSrc {
-  const float *flow;
-  __device__ __forceinline__ void at(long p, int /*pair*/, int /*x*/, int /*y*/, float &u, float &v) const
-  {
-    u = flow[2 * p]; v = flow[2 * p + 1];
-  }
-};
-
-// The coarse flow of a context (n x hl x wl x 2): upsample_crop4_kernel's value at output pixel (x, y) of the pair.
-struct UpsampleSrc {
-  const float *flow;
-  long in_stride;          // floats per pair: wl * hl * 2
-  int wl, hl, sc_l, x0, y0;
-  __device__ __forceinline__ void coord(int d, int n, int &s0, int &s1, float &fr) const
-  {
-    const int N = 2 * d + 1 - (1 << sc_l);
-    float fc = (float)N * __builtin_ldexpf(1.0f, -(sc_l + 1));
-    int si = (int)floorf(fc); fc -= si;
-    if (si < 0) { fc = 0; si = 0; }
-    if (si >= n - 1) { fc = 0; si = n - 1; }
-    s0 = si; s1 = si + 1 < n ? si + 1 : n - 1; fr = fc;
-  }
-  __device__ __forceinline__ void at(long /*p*/, int pair, int x, int y, float &u, float &v) const
-  {
-    int sy, sy1, sx, sx1; float fy, fx;
-    coord(y + y0, hl, sy, sy1, fy);
-    coord(x + x0, wl, sx, sx1, fx);
-    const float *f = flow + (size_t)pair * in_stride;
-    const float scf = (float)(1 << sc_l);
-    float r[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      float v00 = f[2 * ((size_t)sy * wl + sx) + c], v01 = f[2 * ((size_t)sy * wl + sx1) + c];
-      float v10 = f[2 * ((size_t)sy1 * wl + sx) + c], v11 = f[2 * ((size_t)sy1 * wl + sx1) + c];
-      if (sc_l != 0) { v00 *= scf; v01 *= scf; v10 *= scf; v11 *= scf; }
-      const float a0 = v00 * (1.f - fx) + v01 * fx;
-      const float a1 = v10 * (1.f - fx) + v11 * fx;
-      r[c] = a0 * (1.f - fy) + a1 * fy;
-    }
-    u = r[0]; v = r[1];
-  }
-};
 
 __device__ __forceinline__ unsigned fc_wave_max(unsigned v)
 {

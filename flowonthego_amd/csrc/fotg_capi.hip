@@ -252,6 +252,8 @@ int fotg_create(const fotg_params *p, int w_org, int h_org, int device, int max_
   if (p->depth && p->usetvref && p->sor_mode != FOTG_SOR_LEXICOGRAPHIC) return FOTG_ERR_UNSUPPORTED;
   if (p->sor_mode < FOTG_SOR_LEXICOGRAPHIC || p->sor_mode > FOTG_SOR_POINT) return FOTG_ERR_ARG;      // (an unknown value would run the lexicographic arithmetic without its buffers)
   if (p->u8_color < 0 || p->u8_color > 2 || (p->u8_color && p->noc != 1)) return FOTG_ERR_ARG;
+  if (p->bidir != 0 && p->bidir != 1) return FOTG_ERR_ARG;
+  if (p->bidir && p->depth) return FOTG_ERR_UNSUPPORTED;        // no agreed meaning of the backward camera clamp for a swapped stereo pair
   ON_DEVICE(device);
   fotg_ctx *c = new (std::nothrow) fotg_ctx();
   if (!c) return FOTG_ERR_ARG;
@@ -307,7 +309,7 @@ int fotg_create(const fotg_params *p, int w_org, int h_org, int device, int max_
       ALLOC(c->flow[l], B * g.w * g.h * 2 * sizeof(float));
       ALLOC(c->p_iter[l], B * g.nop * 2 * sizeof(float));
       ALLOC(c->pweight[l], B * g.nop * (size_t)(p->ps * p->ps * c->noc) * sizeof(float));
-      if (p->usefbcon) {
+      if (p->usefbcon || p->bidir) {
         ALLOC(c->dx1[l], bytes);
         ALLOC(c->dy1[l], bytes);
         ALLOC(c->flow_bw[l], B * g.w * g.h * 2 * sizeof(float));
@@ -1333,16 +1335,21 @@ int fotg_varref_plane(fotg_ctx *c, int pair, const char *name, int l, float *hos
 }  // extern "C"
 // I1 == nullptr: sequence mode -- I0 holds n+1 consecutive frames, pair k is (frame k, frame k+1); every frame's pyramid
 // is built once (with gradients) and serves as the target of pair k-1 and the template source of pair k.
+// outflow_bw != nullptr: bidirectional (fotg_calc_bidir, contexts created with fotg_params::bidir) -- the backward flow of every
+// pair (template = its frame 1, target = its frame 0, initialised from initflow_bw) runs on the backward grid view at every level,
+// the finest one included, with the same steps as the forward one; each frame's pyramid is built once, with gradients.
 template <typename T>
-static int calc_range(fotg_ctx *c, int n, const T *I0, const T *I1, const float *initflow, float *outflow, hipStream_t stream)
+static int calc_range(fotg_ctx *c, int n, const T *I0, const T *I1, const float *initflow, float *outflow, hipStream_t stream,
+                      const float *initflow_bw = nullptr, float *outflow_bw = nullptr)
 {
   int st;
-  const bool seq = I1 == nullptr, fb = c->p.usefbcon != 0;
+  const bool seq = I1 == nullptr, fb = c->p.usefbcon != 0, bidir = outflow_bw != nullptr;
   const int nimg = seq ? n + 1 : n;
-  // stage timing for the reference's verbosity output: events on the launch stream (not while a graph is being captured)
+  // stage timing for the reference's verbosity output: events on the launch stream (not while a graph is being captured).  A
+  // bidirectional call runs two flows per stage, which the reference's lines have no field for: it records no times.
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(stream, &cap);
-  const bool timing = c->verbosity > 0 && cap == hipStreamCaptureStatusNone;
+  const bool timing = c->verbosity > 0 && cap == hipStreamCaptureStatusNone && !bidir;
   int nev = 0;
   auto mark = [&]() {
     if (!timing || nev >= (int)(sizeof(c->tev) / sizeof(c->tev[0]))) return;
@@ -1353,7 +1360,7 @@ static int calc_range(fotg_ctx *c, int n, const T *I0, const T *I1, const float 
   // the backward grid lives in a view of the context whose grid arrays are the *_bw ones (nothing is owned by the view)
   fotg_ctx *vb = nullptr;
   struct ViewGuard { fotg_ctx *&v; ~ViewGuard() { free(v); } } guard{vb};
-  if (fb) {
+  if (fb || bidir) {
     vb = (fotg_ctx *)malloc(sizeof(fotg_ctx));
     if (!vb) return FOTG_ERR_ARG;
     memcpy((void *)vb, (const void *)c, sizeof(fotg_ctx));
@@ -1361,10 +1368,12 @@ static int calc_range(fotg_ctx *c, int n, const T *I0, const T *I1, const float 
     for (int l = c->p.sc_l; l <= c->p.sc_f; ++l) {
       vb->p_iter[l] = c->p_iter_bw[l]; vb->pweight[l] = c->pweight_bw[l];
       memset((void *)&vb->gs[l], 0, sizeof(GridState));
-      vb->gs[l].camlr = 1;                                         // kroeger/oflow.cpp:157,165: the backward grid is the right camera
+      // kroeger/oflow.cpp:157,165: the backward grid of the merge is the right camera; a plain bidirectional call's backward
+      // grid is what a one-direction call on the swapped pair runs (camlr only clamps in depth mode, which bidir refuses)
+      vb->gs[l].camlr = fb ? 1 : c->gs[l].camlr;
     }
   }
-  if (fb && !seq) {
+  if ((fb || bidir) && !seq) {
     // both frames need gradients: two template-type pyramids (the second one into the frame-1 buffers)
     if ((st = pyramid_any<T>(c, n, I0, (const T *)nullptr, stream))) return st;
     fotg_ctx *v1 = (fotg_ctx *)malloc(sizeof(fotg_ctx));
@@ -1394,14 +1403,37 @@ static int calc_range(fotg_ctx *c, int n, const T *I0, const T *I1, const float 
       if ((st = fotg_grid_optimize(vb, l, n, stream))) return st;
       mark();
       float *out = (l == c->p.sc_l) ? outflow : c->flow[l];
+      // (bidir: the backward flow of the finest level too, into outflow_bw)
+      float *out_bw = (l == c->p.sc_l) ? outflow_bw : c->flow_bw[l];
       if ((st = aggregate_impl(c, l, n, c->p_iter[l], c->pweight[l], c->p_iter_bw[l], c->pweight_bw[l], out, stream))) return st;
-      if (l > c->p.sc_l && (st = aggregate_impl(c, l, n, c->p_iter_bw[l], c->pweight_bw[l], c->p_iter[l], c->pweight[l], c->flow_bw[l], stream))) return st;
+      if (out_bw && (st = aggregate_impl(c, l, n, c->p_iter_bw[l], c->pweight_bw[l], c->p_iter[l], c->pweight[l], out_bw, stream))) return st;
       mark();
       if (c->p.usetvref) {
         if ((st = varref_dispatch(c, l, n, c->im[0][l], tgt, ls, out, stream, 0))) return st;
-        if (l > c->p.sc_l && (st = varref_dispatch(c, l, n, tgt, c->im[0][l], ls, c->flow_bw[l], stream, 1))) return st;
+        if (out_bw && (st = varref_dispatch(c, l, n, tgt, c->im[0][l], ls, out_bw, stream, 1))) return st;
       }
       mark();
+      continue;
+    }
+    if (bidir) {
+      // two independent directions on one workspace, one after the other: the forward one exactly as below, then the backward
+      // one on the view -- template = the pair's frame 1 (with the gradients of its template-type pyramid), target = frame 0
+      const float *tx = seq ? c->dx0[l] + ls : c->dx1[l], *ty = seq ? c->dy0[l] + ls : c->dy1[l];
+      float *out = (l == c->p.sc_l) ? outflow : c->flow[l], *out_bw = (l == c->p.sc_l) ? outflow_bw : c->flow_bw[l];
+      if ((st = fotg_grid_init(c, l, n, c->im[0][l], c->dx0[l], c->dy0[l], ls, stream))) return st;
+      if ((st = fotg_grid_set_target(c, l, tgt, ls))) return st;
+      if (l < c->p.sc_f) { if ((st = fotg_grid_init_from_coarser(c, l, n, c->flow[l + 1], stream))) return st; }
+      else if (initflow) { if ((st = fotg_grid_init_from_coarser(c, l, n, initflow, stream))) return st; }
+      if ((st = fotg_grid_optimize(c, l, n, stream))) return st;
+      if ((st = aggregate_impl(c, l, n, c->p_iter[l], c->pweight[l], nullptr, nullptr, out, stream))) return st;
+      if (c->p.usetvref && (st = varref_dispatch(c, l, n, c->im[0][l], tgt, ls, out, stream, 0))) return st;
+      if ((st = fotg_grid_init(vb, l, n, tgt, tx, ty, ls, stream))) return st;
+      if ((st = fotg_grid_set_target(vb, l, c->im[0][l], ls))) return st;
+      if (l < c->p.sc_f) { if ((st = fotg_grid_init_from_coarser(vb, l, n, c->flow_bw[l + 1], stream))) return st; }
+      else if (initflow_bw) { if ((st = fotg_grid_init_from_coarser(vb, l, n, initflow_bw, stream))) return st; }
+      if ((st = fotg_grid_optimize(vb, l, n, stream))) return st;
+      if ((st = aggregate_impl(c, l, n, c->p_iter_bw[l], c->pweight_bw[l], nullptr, nullptr, out_bw, stream))) return st;
+      if (c->p.usetvref && (st = varref_dispatch(c, l, n, tgt, c->im[0][l], ls, out_bw, stream, 0))) return st;
       continue;
     }
     if ((st = fotg_grid_init(c, l, n, c->im[0][l], c->dx0[l], c->dy0[l], c->lev_stride[l], stream))) return st;
@@ -1455,6 +1487,34 @@ int fotg_calc_batch_u8(fotg_ctx *c, int n, const unsigned char *I0, const unsign
   if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
   ON_DEVICE(c->device);
   return calc_range<unsigned char>(c, n, I0, I1, initflow, outflow, (hipStream_t)stream);
+}
+
+/* bidirectional flow: outflow == fotg_calc_batch(I0, I1, initflow), outflow_bw == fotg_calc_batch(I1, I0, initflow_bw), bit for bit,
+ * from one pyramid per frame.  FOTG_ERR_ARG: a context created without fotg_params::bidir, a null frame or output pointer, or an
+ * initflow with usefbcon (the merge couples the directions; its one-direction form initialises only the forward grid). */
+static int bidir_args(fotg_ctx *c, int n, const void *I0, const void *I1, const float *initflow, const float *initflow_bw,
+                      const float *outflow, const float *outflow_bw)
+{
+  if (!c || !c->p.bidir || !I0 || !I1 || !outflow || !outflow_bw) return FOTG_ERR_ARG;
+  if (c->p.usefbcon && (initflow || initflow_bw)) return FOTG_ERR_ARG;
+  if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
+  return FOTG_OK;
+}
+
+int fotg_calc_bidir(fotg_ctx *c, int n, const float *I0, const float *I1, const float *initflow, const float *initflow_bw,
+                    float *outflow, float *outflow_bw, void *stream)
+{
+  int st = bidir_args(c, n, I0, I1, initflow, initflow_bw, outflow, outflow_bw); if (st) return st;
+  ON_DEVICE(c->device);
+  return calc_range<float>(c, n, I0, I1, initflow, outflow, (hipStream_t)stream, initflow_bw, outflow_bw);
+}
+
+int fotg_calc_bidir_u8(fotg_ctx *c, int n, const unsigned char *I0, const unsigned char *I1, const float *initflow,
+                       const float *initflow_bw, float *outflow, float *outflow_bw, void *stream)
+{
+  int st = bidir_args(c, n, I0, I1, initflow, initflow_bw, outflow, outflow_bw); if (st) return st;
+  ON_DEVICE(c->device);
+  return calc_range<unsigned char>(c, n, I0, I1, initflow, outflow, (hipStream_t)stream, initflow_bw, outflow_bw);
 }
 
 /* ---- batches in flight ---------------------------------------------------------------------------------------------
@@ -1759,6 +1819,22 @@ int fotg_calc_sequence_u8(fotg_ctx *c, int n_frames, const unsigned char *frames
   if (n_frames < 2 || n_frames - 1 > c->max_batch) return FOTG_ERR_BATCH;
   ON_DEVICE(c->device);
   return calc_range<unsigned char>(c, n_frames - 1, frames, nullptr, initflow, outflow, (hipStream_t)stream);
+}
+
+/* the sequence form: pair k = (frame k, frame k+1) forward, (frame k+1, frame k) backward; every frame's pyramid once */
+int fotg_calc_sequence_bidir(fotg_ctx *c, int n_frames, const float *frames, const float *initflow, const float *initflow_bw,
+                             float *outflow, float *outflow_bw, void *stream)
+{
+  int st = bidir_args(c, n_frames - 1, frames, frames, initflow, initflow_bw, outflow, outflow_bw); if (st) return st;
+  ON_DEVICE(c->device);
+  return calc_range<float>(c, n_frames - 1, frames, nullptr, initflow, outflow, (hipStream_t)stream, initflow_bw, outflow_bw);
+}
+int fotg_calc_sequence_bidir_u8(fotg_ctx *c, int n_frames, const unsigned char *frames, const float *initflow, const float *initflow_bw,
+                                float *outflow, float *outflow_bw, void *stream)
+{
+  int st = bidir_args(c, n_frames - 1, frames, frames, initflow, initflow_bw, outflow, outflow_bw); if (st) return st;
+  ON_DEVICE(c->device);
+  return calc_range<unsigned char>(c, n_frames - 1, frames, nullptr, initflow, outflow, (hipStream_t)stream, initflow_bw, outflow_bw);
 }
 
 long fotg_debug_counter(const char *name)

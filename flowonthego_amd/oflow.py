@@ -175,6 +175,54 @@ class OFClass:
         check(fn(self._h, n + 1, _ptr(frames), _ptr(initflow), _ptr(outflow), _stream(self.device)))
         return outflow
 
+    # -- both directions (op.bidir) --------------------------------------------------------------------------
+    def _bidir_args(self, n, outflow, outflow_bw, initflow, initflow_bw):
+        if not self.op.bidir:
+            raise FotgError("calc_bidirectional needs a context created with opt_params.bidir = True")
+        outflow, initflow = self._flow_args(n, outflow, initflow)
+        outflow_bw, initflow_bw = self._flow_args(n, outflow_bw, initflow_bw)
+        return outflow, outflow_bw, initflow, initflow_bw
+
+    def calc_bidirectional(self, I0, I1, initflow=None, initflow_bw=None, outflow=None, outflow_bw=None):
+        """both directions of n pairs from one pyramid per frame -> (fw, bw): fw == calc_batch(I0, I1, initflow) and
+        bw == calc_batch(I1, I0, initflow_bw), bit for bit"""
+        I0, I1 = _dev_f32(I0, "I0", self.device), _dev_f32(I1, "I1", self.device)
+        n = I0.shape[0]
+        exp = (n, self.height_org, self.width_org) + ((self.op.channels,) if self.op.channels > 1 else ())
+        if (tuple(I0.shape) != exp and tuple(I0.shape) != exp + (1,)) or I1.shape != I0.shape:
+            raise FotgError("frame shape %s does not match the configured %s" % (tuple(I0.shape), exp))
+        fw, bw, ifw, ibw = self._bidir_args(n, outflow, outflow_bw, initflow, initflow_bw)
+        check(lib().fotg_calc_bidir(self._h, n, _ptr(I0), _ptr(I1), _ptr(ifw), _ptr(ibw), _ptr(fw), _ptr(bw), _stream(self.device)))
+        return fw, bw
+
+    def calc_bidirectional_u8(self, I0, I1, initflow=None, initflow_bw=None, outflow=None, outflow_bw=None):
+        """calc_bidirectional on 8-bit frames (the layout of calc_batch_u8)"""
+        for t, nm in ((I0, "I0"), (I1, "I1")):
+            _dev_f32(t, nm, self.device, dtype=torch.uint8)
+        n = I0.shape[0]
+        exp = (n, self.height_org, self.width_org) + self._u8_channels()
+        if tuple(I0.shape) != exp or I1.shape != I0.shape:
+            raise FotgError("frame shape %s does not match the configured %s" % (tuple(I0.shape), exp))
+        fw, bw, ifw, ibw = self._bidir_args(n, outflow, outflow_bw, initflow, initflow_bw)
+        check(lib().fotg_calc_bidir_u8(self._h, n, _ptr(I0), _ptr(I1), _ptr(ifw), _ptr(ibw), _ptr(fw), _ptr(bw), _stream(self.device)))
+        return fw, bw
+
+    def calc_sequence_bidirectional(self, frames, initflow=None, initflow_bw=None, outflow=None, outflow_bw=None):
+        """video mode, both directions: frames (n+1, ...) float32 or uint8 -> (fw, bw), fw[k] the flow frame k -> k+1 and
+        bw[k] the flow frame k+1 -> k; every frame's pyramid is built once"""
+        if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.is_contiguous() and frames.dtype in (torch.float32, torch.uint8)):
+            raise FotgError("frames must be a contiguous float32 or uint8 CUDA(HIP) tensor")
+        if frames.device != self.device:
+            raise FotgError("frames live on %s, the context on %s" % (frames.device, self.device))
+        n = frames.shape[0] - 1
+        exp = (n + 1, self.height_org, self.width_org) + (self._u8_channels() if frames.dtype == torch.uint8 else ((self.op.channels,) if self.op.channels > 1 else ()))
+        if n < 1 or tuple(frames.shape) != exp:
+            raise FotgError("frame shape %s does not match the configured %s" % (tuple(frames.shape), exp))
+        fw, bw, ifw, ibw = self._bidir_args(n, outflow, outflow_bw, initflow, initflow_bw)
+        fn = lib().fotg_calc_sequence_bidir if frames.dtype == torch.float32 else lib().fotg_calc_sequence_bidir_u8
+        check(fn(self._h, n + 1, _ptr(frames), _ptr(ifw), _ptr(ibw), _ptr(fw), _ptr(bw), _stream(self.device)))
+        return fw, bw
+
     def upsample_crop(self, flow, out=None):
         """src/run_dense.cpp:293-303: x 2^finest, bilinear upsample, crop the padding -> (n, h_org, w_org, 2)"""
         n = flow.shape[0] if isinstance(flow, torch.Tensor) and flow.dim() == 4 else 0
@@ -192,6 +240,11 @@ class OFClass:
         """the Middlebury colour code of upsample_crop(flow), fused: uint8 (n, h_org, w_org, 3) -- flowonthego_amd.color"""
         from .color import upsample_crop_color
         return upsample_crop_color(self, flow, maxmotion=maxmotion, out=out, stats=stats)
+
+    def upsample_crop_fb_check(self, flow, flow_bw, alpha1=0.01, alpha2=0.5, stats=False, fused=False):
+        """forward-backward consistency masks of upsample_crop(flow) / upsample_crop(flow_bw) -- flowonthego_amd.consistency"""
+        from .consistency import upsample_crop_fb_check
+        return upsample_crop_fb_check(self, flow, flow_bw, alpha1=alpha1, alpha2=alpha2, stats=stats, fused=fused)
 
     # -- pyramid (src/oflow.cpp:182-207 ConstructImgPyramids) -----------------------------------------------
     def ConstructImgPyramids(self, I0, I1):

@@ -51,6 +51,7 @@ class opt_params:
     var_ref_inner_iter: int = 1      # kroeger tv_innerit (oflow.h:50, run_dense.cpp:288): inner iterations = var_ref_inner_iter * (level + 1); src/ hard-codes 1
     fast_math: bool = False          # tolerance mode of the patch loop and the refinement's arithmetic (fotg_params::fast_math); False = parity mode
     min_iter: int = -1               # kroeger optparam.min_iter (oflow.h:38); < 0: = grad_descent_iter, as src/ and the operating points have it
+    bidir: bool = False              # fotg_params::bidir: the context can compute both directions (OFClass.calc_bidirectional)
     # derived (src/oflow.cpp:45-48)
     outlier_thresh: float = 0.0
     steps: int = 0
@@ -82,6 +83,7 @@ class opt_params:
         p.depth = int(self.depth_mode)
         p.u8_color = int(self.u8_color)
         p.fast_math = int(self.fast_math)
+        p.bidir = int(self.bidir)
         return p
 
 

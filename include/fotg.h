@@ -88,6 +88,9 @@ typedef struct fotg_params {
                           refinement's cell update (solvers of levels of more than 64 rows) uses fused multiply-adds and its data term
                           (compute_data / compute_smoothness, FDF1.0.1/opticalflow_aux.c:123-165,310-438) v_rcp / v_rsq instead of
                           the IEEE divisions and square roots (csrc/varref_dataterm.inc.h), optical flow only. */
+  int bidir;           /* 0 (default, all operating points): one direction.  1: the context also holds the backward grid and flows
+                          (the usefbcon buffers) that fotg_calc_bidir / fotg_calc_sequence_bidir need; nothing else changes.
+                          FOTG_ERR_UNSUPPORTED with depth. */
 } fotg_params;
 
 typedef struct fotg_ctx fotg_ctx;
@@ -126,6 +129,20 @@ int fotg_calc_batch_u8(fotg_ctx *ctx, int n, const unsigned char *I0, const unsi
 int fotg_calc_sequence(fotg_ctx *ctx, int n_frames, const float *frames, const float *initflow, float *outflow, void *stream);
 int fotg_calc_sequence_u8(fotg_ctx *ctx, int n_frames, const unsigned char *frames, const float *initflow, float *outflow,
                           void *stream);
+/* ---- bidirectional flow (contexts created with fotg_params::bidir = 1; FOTG_ERR_ARG otherwise) ----------------------------
+ * Both directions of every pair from ONE pyramid per frame: outflow == fotg_calc_batch(I0, I1, initflow) and outflow_bw ==
+ * fotg_calc_batch(I1, I0, initflow_bw), bit for bit, in every mode the one-direction call has.  initflow / initflow_bw: NULL or
+ * as fotg_calc_batch's initflow, each for its own direction.  With usefbcon the directions are coupled through the merge;
+ * the contract still holds, with both initflows NULL (FOTG_ERR_ARG otherwise).  Same stream semantics as fotg_calc_batch. */
+int fotg_calc_bidir(fotg_ctx *ctx, int n, const float *I0, const float *I1, const float *initflow, const float *initflow_bw,
+                    float *outflow, float *outflow_bw, void *stream);
+int fotg_calc_bidir_u8(fotg_ctx *ctx, int n, const unsigned char *I0, const unsigned char *I1, const float *initflow,
+                       const float *initflow_bw, float *outflow, float *outflow_bw, void *stream);
+/* video mode: pair k = frames k -> k+1 forward into outflow[k], frames k+1 -> k backward into outflow_bw[k] */
+int fotg_calc_sequence_bidir(fotg_ctx *ctx, int n_frames, const float *frames, const float *initflow, const float *initflow_bw,
+                             float *outflow, float *outflow_bw, void *stream);
+int fotg_calc_sequence_bidir_u8(fotg_ctx *ctx, int n_frames, const unsigned char *frames, const float *initflow,
+                                const float *initflow_bw, float *outflow, float *outflow_bw, void *stream);
 /* ---- batches in flight (no reference equivalent: the reference's calc() is synchronous, one pair at a time) -------------
  * A pipe owns `depth` engine contexts, each on an internal non-blocking stream.  fotg_pipe_submit enqueues one batch exactly
  * like fotg_calc_batch (same arguments, same bits) on the next context in turn and returns at once; up to `depth` batches
@@ -241,6 +258,29 @@ int fotg_flow_color(int device, int n, const float *flow, int w, int h, float ma
  * fly: rgb (n x h_org x w_org x 3) == fotg_flow_color(fotg_upsample_crop(flow)) byte for byte, without writing the full-resolution
  * flow.  FOTG_ERR_ARG: n < 1 or n > max_batch, a null pointer, a depth-mode context (one channel: no colour code for it). */
 int fotg_upsample_crop_color(fotg_ctx *ctx, int n, const float *flow, float maxmotion, unsigned char *rgb, float *stats, void *stream);
+
+/* ---- forward-backward consistency (Sundaram, Brox & Keutzer, ECCV 2010), csrc/fbcheck.hip.h -----------------------------
+ * Per pixel (x, y) of a w x h pair (F, B), all arithmetic f32, each operation rounded on its own (no contraction), in this order:
+ *   u, v = F[y][x]
+ *   if !isfinite(u) || !isfinite(v):                                   code 3 (unknown)
+ *   X = (float)x + u;  Y = (float)y + v
+ *   if !(X >= 0 && X <= w-1 && Y >= 0 && Y <= h-1):                    code 2 (leaves the frame)
+ *   x0 = min((int)floorf(X), w-1); x1 = min(x0+1, w-1); ax = X - (float)x0      (y0, y1, ay alike)
+ *   per channel: r0 = B[y0][x0]*(1-ax) + B[y0][x1]*ax;  r1 = B[y1][x0]*(1-ax) + B[y1][x1]*ax;  b = r0*(1-ay) + r1*ay
+ *   du = u + bu;  dv = v + bv
+ *   lhs = du*du + dv*dv;  rhs = alpha1*((u*u + v*v) + (bu*bu + bv*bv)) + alpha2
+ *   code = lhs < rhs ? 0 (consistent) : 1 (occluded / inconsistent; a NaN in B gives 1)
+ * Defaults alpha1 = 0.01, alpha2 = 0.5.
+ * flow, flow_bw: n x h x w x 2 f32 on the device.  mask (frame-0 pixels, F against B), mask_bw (frame-1 pixels, B against F):
+ * n x h x w uint8, either may be NULL.  counts: NULL or n x 2 x 4 uint32 -- per image and direction (0 = mask, 1 = mask_bw)
+ * the number of pixels of each code, zeroed by the call.  Asynchronous on `stream`. */
+int fotg_fb_check(int device, int n, const float *flow, const float *flow_bw, int w, int h, float alpha1, float alpha2,
+                  unsigned char *mask, unsigned char *mask_bw, unsigned *counts, void *stream);
+/* The same from the coarse flows of a context (n x hl x wl x 2 each, fotg_out_size), upsampled and cropped on the fly: masks
+ * (n x h_org x w_org) byte-identical to fotg_fb_check(fotg_upsample_crop(flow), fotg_upsample_crop(flow_bw)), without writing
+ * either full-resolution flow.  FOTG_ERR_ARG: n < 1 or n > max_batch, a null flow, a depth-mode context. */
+int fotg_upsample_crop_fb_check(fotg_ctx *ctx, int n, const float *flow, const float *flow_bw, float alpha1, float alpha2,
+                                unsigned char *mask, unsigned char *mask_bw, unsigned *counts, void *stream);
 
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."

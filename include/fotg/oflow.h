@@ -72,6 +72,16 @@ class OFClass {
   // video: n_frames consecutive frames -> n_frames - 1 flows, every frame's pyramid built once
   void calc_sequence(int n_frames, const float *frames, const float *initflow, float *outflow_dev, void *stream = nullptr)
   { fotgCheck(fotg_calc_sequence(ctx, n_frames, frames, initflow, outflow_dev, stream), "OFClass::calc_sequence"); }
+  // both directions (op.bidir): outflow_dev as calc_batch(I0, I1), outflow_bw_dev as calc_batch(I1, I0), one pyramid per frame
+  void calc_bidirectional(int n, const float *_I0, const float *_I1, const float *initflow, const float *initflow_bw,
+                          float *outflow_dev, float *outflow_bw_dev, void *stream = nullptr)
+  { fotgCheck(fotg_calc_bidir(ctx, n, _I0, _I1, initflow, initflow_bw, outflow_dev, outflow_bw_dev, stream), "OFClass::calc_bidirectional"); }
+  void calc_sequence_bidirectional(int n_frames, const float *frames, const float *initflow, const float *initflow_bw,
+                                   float *outflow_dev, float *outflow_bw_dev, void *stream = nullptr)
+  {
+    fotgCheck(fotg_calc_sequence_bidir(ctx, n_frames, frames, initflow, initflow_bw, outflow_dev, outflow_bw_dev, stream),
+              "OFClass::calc_sequence_bidirectional");
+  }
 
   fotg_ctx *handle() { return ctx; }
   PatGridClass *GetGrid(int scale) { return grid[scale - op.finest_scale]; }

@@ -56,6 +56,7 @@ typedef struct {
   int var_ref_inner_iter = 1; // kroeger tv_innerit (oflow.h:50, run_dense.cpp:288): inner fixed-point iterations = var_ref_inner_iter * (level + 1)
                      // (refine_variational.cpp:36); src/ hard-codes 1 (src/refine_variational.cpp:41)
   bool fast_math = false; // tolerance mode of the patch loop and the refinement's arithmetic (fotg_params::fast_math): flows within 1e-3 px (mean) of the parity mode
+  bool bidir = false; // fotg_params::bidir: the context can compute both directions (OFClass::calc_bidirectional)
 } opt_params;
 
 inline fotg_params to_fotg(const opt_params &op)
@@ -73,6 +74,7 @@ inline fotg_params to_fotg(const opt_params &op)
   p.costfct = op.cost_func; p.normoutlier = op.norm_outlier; p.usefbcon = op.use_fbcon; p.depth = op.depth_mode;
   p.u8_color = op.u8_color;
   p.fast_math = op.fast_math;
+  p.bidir = op.bidir;
   return p;
 }
 

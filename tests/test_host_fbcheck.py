@@ -1,0 +1,67 @@
+"""The consistency check's tools: examples/fb_check.cpp compiles and links against the C++ shim (no GPU needed), and the
+python -m flowonthego_amd.fb_check CLI writes the mask PNG of the numpy restatement (GPU)."""
+import os
+import struct
+import subprocess
+import sys
+import zlib
+
+import numpy as np
+import pytest
+
+import fbcheck_ref as R
+from conftest import ROOT
+
+
+def test_fb_check_example_builds(tmp_path):
+    import flowonthego_amd as F
+    F.lib()
+    from test_host import _build_example
+    assert os.path.exists(_build_example(tmp_path, "fb_check"))
+
+
+def test_cli_argument_errors(tmp_path):
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for args in ([], ["a.flo"], ["a.flo", "b.flo"], ["a.flo", "b.flo", "c.png", "--alpha1", "x"]):
+        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.fb_check"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
+        assert r.returncode != 0 and "usage" in r.stderr, args
+
+
+def read_png_rgb(path):
+    """the single-IDAT, filter-0 RGB PNGs color.write_png writes"""
+    data = open(path, "rb").read()
+    assert data[:8] == b"\x89PNG\r\n\x1a\n"
+    pos, idat, w, h = 8, b"", None, None
+    while pos < len(data):
+        n, = struct.unpack(">I", data[pos:pos + 4])
+        tag, body = data[pos + 4:pos + 8], data[pos + 8:pos + 8 + n]
+        if tag == b"IHDR":
+            w, h = struct.unpack(">II", body[:8])
+        elif tag == b"IDAT":
+            idat += body
+        pos += 12 + n
+    raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + 3 * w)
+    assert not raw[:, 0].any()
+    return raw[:, 1:].reshape(h, w, 3)
+
+
+@pytest.mark.gpu
+def test_cli_writes_the_mask_of_the_restatement(tmp_path):
+    from flowonthego_amd.flo import write_flo
+    rng = np.random.default_rng(9)
+    h, w = 23, 41
+    fw = (rng.standard_normal((h, w, 2)) * 3).astype(np.float32)
+    bw = (-fw + rng.standard_normal((h, w, 2)).astype(np.float32) * 0.4).astype(np.float32)
+    fw[0, 0] = (np.nan, 0)
+    a, b, out = (str(tmp_path / n) for n in ("fw.flo", "bw.flo", "mask.png"))
+    write_flo(a, fw)
+    write_flo(b, bw)
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.fb_check", a, b, out, "--alpha1", "0.02", "--alpha2", "0.4"],
+                       capture_output=True, text=True, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr
+    want = R.fb_code(fw, bw, 0.02, 0.4)
+    palette = np.array([(255, 255, 255), (255, 0, 0), (0, 0, 255), (0, 0, 0)], np.uint8)
+    assert np.array_equal(read_png_rgb(out), palette[want])
+    fr = [float(t) for t in r.stdout.split()[1::2]]
+    assert np.allclose(fr, np.bincount(want.ravel(), minlength=4) / want.size, atol=1e-4)
