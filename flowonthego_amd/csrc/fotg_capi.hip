@@ -11,6 +11,7 @@
 #include <mutex>
 #include <new>
 #include "common.h"
+#include "pipe_tickets.h"
 #include "pyramid.hip.h"
 #include "lk.hip.h"
 #include "lk_fast.hip.h"
@@ -1546,7 +1547,6 @@ struct fotg_pipe {
   // re-recorded belongs to a later batch of the SAME slot's stream, which still covers the older ticket.
   hipEvent_t done[4 * FOTG_PIPE_MAX_DEPTH];
   int nring;
-  long submitted;
   // Self-healing host waits.  The tile solver's bounded waits (varref_tiles.hip.h) raise ONE word per context; a host wait that finds
   // it set cannot tell which of the context's batches raised it, so it recomputes every batch of that context that has not been
   // verified yet -- on the solver path without inter-workgroup waits (FOTG_VR_PATH=1's) -- from the arguments kept here.  The caller's
@@ -1554,11 +1554,8 @@ struct fotg_pipe {
   // A ticket is HEALABLE only while its buffers are contractually still in place: submitted without FOTG_SUBMIT_NO_RECOMPUTE and not yet
   // handed out through fotg_pipe_wait(host_wait = 0) / fotg_pipe_ticket_event (whoever waits that way may free or reuse the frames and the
   // outflow as soon as THEIR wait returns, without the pipe knowing).  Suspects that are not healable are reported, never recomputed.
-  struct Args { int n, u8, healable; const void *I0, *I1; const float *initflow; float *out; } args[4 * FOTG_PIPE_MAX_DEPTH];
-  signed char tstatus[4 * FOTG_PIPE_MAX_DEPTH];      // per ticket (of the last nring): 0 unknown, 1 good, 2 stalled and not recomputed
-  long verified[FOTG_PIPE_MAX_DEPTH];                // per slot: tickets below this one are known good (or have their status in tstatus / lost_*)
-  long lost_lo[FOTG_PIPE_MAX_DEPTH], lost_hi[FOTG_PIPE_MAX_DEPTH];   // per slot: tickets of [lost_lo, lost_hi) were suspects of a flagged stall when the ring
-                                                     // (the last 4 * depth submissions) no longer described them: never recomputed, FOTG_ERR_STALL on every wait
+  struct Args { int n, u8; const void *I0, *I1; const float *initflow; float *out; } args[4 * FOTG_PIPE_MAX_DEPTH];
+  fotg_tickets::PipeBook book;                       // which tickets are healable / suspects / stalled, and what a wait reports (pipe_tickets.h)
   long healed;                                       // batches recomputed so far
   std::mutex *mu;                                    // submit / verification (fotg_node waits from another thread than the one that submits)
 };
@@ -1592,10 +1589,10 @@ int fotg_pipe_create(const fotg_params *p, int w_org, int h_org, int device, int
                       "must be >= %d in the environment BEFORE libamdhip64 is loaded (a setenv after that is not seen by the runtime, and "
                       "not by this check either); otherwise slots share queues and do not overlap\n", depth, depth + 1);
   }
-  fotg_pipe *q = new (std::nothrow) fotg_pipe();
+  fotg_pipe *q = new (std::nothrow) fotg_pipe();          // (value-initialised: every handle and counter starts at zero)
   if (!q) return FOTG_ERR_ARG;
-  memset((void *)q, 0, sizeof(*q));
   q->device = device; q->depth = depth; q->nring = 4 * depth;
+  q->book = fotg_tickets::PipeBook(depth);
   q->mu = new (std::nothrow) std::mutex();
   if (!q->mu) { delete q; return FOTG_ERR_ARG; }
   // the slots' streams first and back to back, so that the runtime spreads them over its hardware queues
@@ -1645,53 +1642,35 @@ static int recompute_safe(fotg_ctx *c, int n, const T *I0, const T *I1, const fl
   return st;
 }
 
-// After the host has synchronised with ticket t (slot k): classify the unverified tickets of the slot.  heal = recompute the
-// suspects (1) or only mark them (0).  Called with the pipe's mutex held.
-static int pipe_verify(fotg_pipe *q, long t, int heal, int *newly_stalled = nullptr)
+// slot k's stall word: FOTG_OK = clear; FOTG_ERR_STALL = it was set, and the slot has been synchronised and the word cleared
+static int take_flag(fotg_pipe *q, int k)
 {
-  const int k = (int)(t % q->depth);
   fotg_ctx *c = q->ctx[k];
-  auto known = [&](long u) { return u >= q->submitted - q->nring; };       // (the ring still describes ticket u)
-  // status of a ticket that has been classified: from the ring while it is there, afterwards from the slot's range of lost suspects
-  auto status_of = [&](long u) {
-    if (known(u)) return q->tstatus[u % q->nring] == 2 ? FOTG_ERR_STALL : FOTG_OK;
-    return u >= q->lost_lo[k] && u < q->lost_hi[k] ? FOTG_ERR_STALL : FOTG_OK;
-  };
-  if (t < q->verified[k]) return status_of(t);
-  const bool flagged = c->stall_host && *(volatile int *)c->stall_host != 0;
-  if (!flagged) {
-    // everything of this slot that has completed so far is good: at least the tickets up to t
-    for (long u = q->verified[k]; u <= t; u += 1) if (u % q->depth == k && known(u)) q->tstatus[u % q->nring] = 1;
-    q->verified[k] = t + 1;
-    return FOTG_OK;
-  }
-  // the word does not say which batch of this context raised it: all of them that are not verified yet are suspects
+  if (!c->stall_host || *(volatile int *)c->stall_host == 0) return FOTG_OK;
   HIPCHK(hipStreamSynchronize(q->stream[k]));
   *(volatile int *)c->stall_host = 0;
   ++c->stalls;
-  for (long u = q->verified[k]; u < q->submitted; ++u) {
-    if (u % q->depth != k) continue;
-    if (!known(u)) {
-      // more than 4 * depth submissions ago: its arguments are gone, so it can be neither recomputed nor cleared -- it stays a suspect
-      // (a node submits an unbounded number of pieces per job; ADVICE round 5: such a ticket used to be waited for as FOTG_OK)
-      if (q->lost_hi[k] <= q->lost_lo[k]) { q->lost_lo[k] = u; q->lost_hi[k] = u + 1; }
-      else { if (u < q->lost_lo[k]) q->lost_lo[k] = u; if (u + 1 > q->lost_hi[k]) q->lost_hi[k] = u + 1; }
-      if (newly_stalled) ++*newly_stalled;
-      continue;
-    }
-    int st = FOTG_ERR_STALL;
-    const fotg_pipe::Args &ar = q->args[u % q->nring];
-    if (heal && ar.healable) {
-      st = ar.u8 ? recompute_safe<unsigned char>(c, ar.n, (const unsigned char *)ar.I0, (const unsigned char *)ar.I1, ar.initflow, ar.out, q->stream[k])
-                 : recompute_safe<float>(c, ar.n, (const float *)ar.I0, (const float *)ar.I1, ar.initflow, ar.out, q->stream[k]);
-      if (st == FOTG_OK) ++q->healed;
-      else if (st != FOTG_ERR_STALL) return st;
-    }
-    q->tstatus[u % q->nring] = st == FOTG_OK ? 1 : 2;
-    if (st != FOTG_OK && newly_stalled) ++*newly_stalled;
-  }
-  q->verified[k] = q->submitted;
-  return status_of(t);
+  return FOTG_ERR_STALL;
+}
+
+// ticket u again from the arguments of its submit (pipe_tickets.h asks only for tickets whose buffers are still in place)
+static int recompute_ticket(fotg_pipe *q, long u)
+{
+  const int k = (int)(u % q->depth);
+  fotg_ctx *c = q->ctx[k];
+  const fotg_pipe::Args &ar = q->args[u % q->nring];
+  const int st = ar.u8 ? recompute_safe<unsigned char>(c, ar.n, (const unsigned char *)ar.I0, (const unsigned char *)ar.I1, ar.initflow, ar.out, q->stream[k])
+                       : recompute_safe<float>(c, ar.n, (const float *)ar.I0, (const float *)ar.I1, ar.initflow, ar.out, q->stream[k]);
+  if (st == FOTG_OK) ++q->healed;
+  return st;
+}
+
+// After the host has synchronised with ticket t (slot k): settle the unverified tickets of the slot (pipe_tickets.h decides; the stall
+// word, the synchronisation and the recompute are here).  heal = recompute the suspects that may be recomputed (1) or only mark
+// them (0).  Called with the pipe's mutex held.
+static int pipe_verify(fotg_pipe *q, long t, int heal)
+{
+  return q->book.verify(t, heal, [&](int k) { return take_flag(q, k); }, [&](long u) { return recompute_ticket(q, u); });
 }
 
 template <typename T>
@@ -1699,7 +1678,7 @@ static int pipe_submit(fotg_pipe *q, int n, const T *I0, const T *I1, const floa
 {
   if (!q || !I0 || !I1 || !outflow) return FOTG_ERR_ARG;
   std::lock_guard<std::mutex> lock(*q->mu);
-  const int k = (int)(q->submitted % q->depth);
+  const int k = (int)(q->book.submitted % q->depth);
   fotg_ctx *c = q->ctx[k];
   if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
   ON_DEVICE(q->device);
@@ -1710,15 +1689,12 @@ static int pipe_submit(fotg_pipe *q, int n, const T *I0, const T *I1, const floa
   }
   const int st = calc_range<T>(c, n, I0, I1, initflow, outflow, q->stream[k]);
   if (st != FOTG_OK) return st;
-  HIPCHK(hipEventRecord(q->done[q->submitted % q->nring], q->stream[k]));
-  {
-    fotg_pipe::Args &ar = q->args[q->submitted % q->nring];
-    ar.n = n; ar.u8 = sizeof(T) == 1; ar.I0 = I0; ar.I1 = I1; ar.initflow = initflow; ar.out = outflow;
-    ar.healable = !(flags & FOTG_SUBMIT_NO_RECOMPUTE);
-    q->tstatus[q->submitted % q->nring] = 0;
-  }
-  if (ticket) *ticket = q->submitted;
-  ++q->submitted;
+  HIPCHK(hipEventRecord(q->done[q->book.submitted % q->nring], q->stream[k]));
+  // (the book folds a stalled ticket whose ring entry this one reuses into its slot's lost set)
+  const long t = q->book.submit(!(flags & FOTG_SUBMIT_NO_RECOMPUTE));
+  fotg_pipe::Args &ar = q->args[t % q->nring];
+  ar.n = n; ar.u8 = sizeof(T) == 1; ar.I0 = I0; ar.I1 = I1; ar.initflow = initflow; ar.out = outflow;
+  if (ticket) *ticket = t;
   return FOTG_OK;
 }
 }  // extern "C++"
@@ -1743,8 +1719,8 @@ int fotg_pipe_submit_ex(fotg_pipe *q, int n, const void *I0, const void *I1, int
 
 int fotg_pipe_wait(fotg_pipe *q, long ticket, void *stream, int host_wait)
 {
-  if (!q || ticket < 0) return FOTG_ERR_ARG;
-  { std::lock_guard<std::mutex> lock(*q->mu); if (ticket >= q->submitted) return FOTG_ERR_ARG; }
+  if (!q) return FOTG_ERR_ARG;
+  { std::lock_guard<std::mutex> lock(*q->mu); if (!q->book.valid(ticket)) return FOTG_ERR_ARG; }
   ON_DEVICE(q->device);
   // (an event re-recorded since -- more than 4 * depth tickets ago -- belongs to a later batch of the same slot's stream: waiting for
   // that one covers the ticket)
@@ -1758,7 +1734,7 @@ int fotg_pipe_wait(fotg_pipe *q, long ticket, void *stream, int host_wait)
   {
     // the caller's stream owns the result from here on and may free / reuse the buffers behind this wait: never recompute into them
     std::lock_guard<std::mutex> lock(*q->mu);
-    if (ticket >= q->submitted - q->nring) q->args[ticket % q->nring].healable = 0;
+    q->book.hand_out(ticket);
   }
   return FOTG_OK;
 }
@@ -1769,11 +1745,11 @@ int fotg_pipe_wait(fotg_pipe *q, long ticket, void *stream, int host_wait)
  * ticket). */
 int fotg_pipe_ticket_event(fotg_pipe *q, long ticket, void **event)
 {
-  if (!q || !event || ticket < 0) return FOTG_ERR_ARG;
+  if (!q || !event) return FOTG_ERR_ARG;
   std::lock_guard<std::mutex> lock(*q->mu);
-  if (ticket >= q->submitted) return FOTG_ERR_ARG;      // (an event of the ring that was never recorded, or belongs to an older batch)
+  if (!q->book.valid(ticket)) return FOTG_ERR_ARG;      // (an event of the ring that was never recorded, or belongs to an older batch)
   *event = (void *)q->done[ticket % q->nring];
-  if (ticket >= q->submitted - q->nring) q->args[ticket % q->nring].healable = 0;       // (handed out: the pipe cannot know when its buffers go)
+  q->book.hand_out(ticket);                             // (handed out: the pipe cannot know when its buffers go)
   return FOTG_OK;
 }
 
@@ -1783,19 +1759,9 @@ int fotg_pipe_sync(fotg_pipe *q)
   ON_DEVICE(q->device);
   for (int k = 0; k < q->depth; ++k) HIPCHK(hipStreamSynchronize(q->stream[k]));
   std::lock_guard<std::mutex> lock(*q->mu);
-  int st = FOTG_OK;
-  for (int k = 0; k < q->depth; ++k) {
-    // the last ticket of slot k (if any): verifying it covers every earlier one of the slot
-    long last = q->submitted - 1;
-    while (last >= 0 && last % q->depth != k) --last;
-    if (last < 0) continue;
-    if (last < q->verified[k]) continue;                  // (all verified; a ticket that could not be recomputed keeps its status for whoever waits for it)
-    int bad = 0;
-    const int sk = pipe_verify(q, last, 1, &bad);
-    if (sk != FOTG_OK) st = sk;
-    else if (bad) st = FOTG_ERR_STALL;
-  }
-  return st;
+  // each slot's last ticket (verifying it covers every earlier one of the slot); a ticket that could not be recomputed keeps its
+  // status for whoever waits for it
+  return q->book.sync([&](int k) { return take_flag(q, k); }, [&](long u) { return recompute_ticket(q, u); });
 }
 
 int fotg_pipe_context(fotg_pipe *q, int slot, fotg_ctx **ctx)

@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/fotg.h"
+#include "pipe_tickets.h"
 
 namespace {
 
@@ -62,8 +63,8 @@ struct fotg_node {
   std::condition_variable cv_job, cv_issued;
   Job ring[RING];
   long submitted = 0, waited = 0;              // jobs handed in; jobs [0, waited) have been waited for (their ring entries are free)
-  int jstatus[RING] = {};                      // final status of job id (id % RING), valid for ids in [waited - RING, waited): a repeated or
-  long jstatus_id[RING];                       // out-of-order wait reports the job's OWN status
+  fotg_tickets::JobBook<RING> jobs;            // final status of the jobs waited for: a repeated or out-of-order wait reports the job's OWN
+                                               // status (the last RING jobs'; a job that stalled reports FOTG_ERR_STALL however old it is)
   int last_hip = 0;                            // HIP error code behind the last FOTG_ERR_HIP a wait returned (raised on a worker thread)
   std::mutex wait_mu;                          // one waiting thread at a time
   bool stop = false;
@@ -261,7 +262,6 @@ int fotg_node_create(const fotg_params *p, int w_org, int h_org, const int *devi
   if (!nd) return FOTG_ERR_ARG;
   nd->ndev = ndev; nd->depth = depth; nd->max_batch = max_batch; nd->w = w_org; nd->h = h_org; nd->noc = p->noc; nd->nch = p->depth ? 1 : 2; nd->u8_color = p->u8_color;
   nd->frame_elems = (size_t)w_org * h_org * p->noc;
-  for (auto &v : nd->jstatus_id) v = -1;
   for (int k = 0; k < ndev; ++k) {
     Slot &s = nd->slot[k];
     s.device = devices[k]; s.index = k;
@@ -348,8 +348,8 @@ int fotg_node_wait(fotg_node *nd, long ticket)
   {
     std::unique_lock<std::mutex> lk(nd->mu);
     if (ticket >= nd->submitted) return FOTG_ERR_ARG;
-    // a job that has been waited for before (tickets are waited for in order): its OWN status, as long as the ring remembers it
-    if (ticket < nd->waited) return nd->jstatus_id[ticket % RING] == ticket ? nd->jstatus[ticket % RING] : FOTG_OK;
+    // a job that has been waited for before (tickets are waited for in order): its OWN status
+    if (ticket < nd->waited) return nd->jobs.status_of(ticket);
     nd->cv_issued.wait(lk, [&] { for (int k = 0; k < nd->ndev; ++k) if (nd->slot[k].issued <= ticket) return false; return true; });
     first = nd->waited;
   }
@@ -373,7 +373,7 @@ int fotg_node_wait(fotg_node *nd, long ticket)
     }
     {
       std::lock_guard<std::mutex> lk(nd->mu);
-      nd->jstatus[id % RING] = st; nd->jstatus_id[id % RING] = id;
+      nd->jobs.record(id, st);
       nd->waited = id + 1;
     }
     if (st != FOTG_OK && worst == FOTG_OK) worst = st;

@@ -89,6 +89,9 @@ class FlowNode:
         return ticket.value, outflow
 
     def wait(self, ticket):
+        """the calling thread waits for job `ticket` and every job before it.  FotgError (FOTG_ERR_STALL: re-submit) for a job
+        with a piece that stalled and could not be recomputed (a pulled scatter piece); the job reports it on every later wait,
+        however many jobs followed, and a good job never does"""
         check(lib().fotg_node_wait(self._h, int(ticket)))
 
     def synchronize(self):

@@ -40,7 +40,8 @@ class FlowPipeline:
         Recompute contract (include/fotg.h): a host wait that finds a stall flag recomputes only batches that have NOT been handed
         to a stream through wait(ticket) -- after wait(ticket) the waiting stream owns the result and the tensors may be freed or
         reused; such a batch is reported (FotgError: FOTG_ERR_STALL) by wait(ticket, host=True) / synchronize(), or through
-        take_stalls().  no_recompute=True says at submit that the buffers will not stay in place.
+        take_stalls().  no_recompute=True says at submit that the buffers will not stay in place.  A batch that was reported
+        stalled is reported by every later host wait for it, and a good one never is, however many batches follow.
         after_current_stream=False starts at once: the caller then guarantees that nothing still enqueued on a torch stream
         writes the frames or touches `outflow` -- including earlier users of memory that torch's caching allocator has
         recycled into these tensors (the pipe's streams are not torch's; synchronize once after allocating the buffers).
@@ -72,7 +73,8 @@ class FlowPipeline:
         return ticket.value, outflow
 
     def wait(self, ticket, host=False):
-        """the current torch stream (host=True: the calling thread) waits for batch `ticket`"""
+        """the current torch stream (host=True: the calling thread) waits for batch `ticket`; host=True raises FotgError
+        (FOTG_ERR_STALL) for a batch that stalled and could not be recomputed, on this and every later wait for it"""
         check(lib().fotg_pipe_wait(self._h, int(ticket), _stream(self.device), 1 if host else 0))
 
     def synchronize(self):

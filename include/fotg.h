@@ -180,8 +180,10 @@ int fotg_pipe_submit_ex(fotg_pipe *pipe, int n, const void *I0, const void *I1, 
  *   place until a ticket has been waited for) and the call succeeds;
  * host_wait = 2: the calling thread waits; a flagged batch is reported (FOTG_ERR_STALL, on every wait for that ticket) instead of
  *   recomputed -- for callers whose frames are not in place any more.
- * Per-ticket state is kept for the last 4 * depth submissions; a suspect older than that keeps FOTG_ERR_STALL (per-slot range).  May be
- * called from another thread than the one that submits. */
+ * A ticket's verdict never changes once a host wait has settled it: a stalled ticket reports FOTG_ERR_STALL from every later host
+ * wait and a good one never does, however many tickets follow (the arguments are kept for the last 4 * depth submissions; the
+ * stalled tickets older than that are kept per slot as disjoint ranges).  May be called from another thread than the one that
+ * submits. */
 int fotg_pipe_wait(fotg_pipe *pipe, long ticket, void *stream, int host_wait);
 /* the calling thread waits for everything submitted so far */
 int fotg_pipe_sync(fotg_pipe *pipe);
@@ -221,8 +223,9 @@ int fotg_node_submit_scatter_u8(fotg_node *node, int n, const unsigned char *I0,
 /* The calling thread waits for job `ticket` and every job before it on all devices.  A piece whose tile solver gave up a bounded
  * wait is recomputed where its frames are still in place (resident shards, the source slot of a scatter: the call then succeeds);
  * pulled pieces of a scatter cannot be (their staging buffers have been recycled): FOTG_ERR_STALL, re-submit the job.  Returns the
- * worst status of the jobs this call covers; every job keeps its own status for later (repeated, out-of-order) waits for it, for
- * the next 16 jobs.  fotg_node_last_hip_error: the HIP error behind the last FOTG_ERR_HIP a wait returned (it was raised on a worker
+ * worst status of the jobs this call covers; every job keeps its own status for later (repeated, out-of-order) waits for it: a job
+ * that ended FOTG_ERR_STALL reports it on every later wait, however many jobs followed, and a good job never does (other errors
+ * are kept for the next 16 jobs).  fotg_node_last_hip_error: the HIP error behind the last FOTG_ERR_HIP a wait returned (it was raised on a worker
  * thread, where fotg_last_hip_error() of the waiting thread does not see it). */
 int fotg_node_wait(fotg_node *node, long ticket);
 int fotg_node_last_hip_error(const fotg_node *node);

@@ -61,6 +61,7 @@ class FlowNode {
     fotgCheck(fotg_node_submit_scatter_u8(node, n, I0, I1, outflow, chunk, &t), "FlowNode::submit_scatter_u8");
     return t;
   }
+  // (a job that ended FOTG_ERR_STALL -- re-submit -- is reported by every later wait for it; a good one never is)
   void wait(long ticket) { fotgCheck(fotg_node_wait(node, ticket), "FlowNode::wait"); }
   void synchronize() { fotgCheck(fotg_node_sync(node), "FlowNode::synchronize"); }
   fotg_node *handle() { return node; }

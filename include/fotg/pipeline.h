@@ -55,6 +55,7 @@ class FlowPipeline {
   // (after wait(ticket, stream) the waiting stream owns the result: the buffers of that batch may be freed or reused behind it, and the
   // pipe will not recompute into them)
   void wait(long ticket, void *stream = nullptr) { fotgCheck(fotg_pipe_wait(pipe, ticket, stream, 0), "FlowPipeline::wait"); }
+  // (a batch reported stalled -- FOTG_ERR_STALL, re-submit -- is reported by every later wait_host for it; a good one never is)
   void wait_host(long ticket) { fotgCheck(fotg_pipe_wait(pipe, ticket, nullptr, 1), "FlowPipeline::wait_host"); }
   void synchronize() { fotgCheck(fotg_pipe_sync(pipe), "FlowPipeline::synchronize"); }
   fotg_pipe *handle() { return pipe; }
