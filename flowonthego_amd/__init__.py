@@ -18,6 +18,9 @@ def __getattr__(name):
     if name in ("fb_check", "upsample_crop_fb_check"):
         from . import consistency
         return getattr(consistency, name)
+    if name in ("warp", "upsample_crop_warp"):
+        import importlib
+        return getattr(importlib.import_module(".warp", __name__), name)
     if name == "FlowPipeline":
         from .pipeline import FlowPipeline
         return FlowPipeline

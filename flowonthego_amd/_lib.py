@@ -69,6 +69,10 @@ SYMBOLS = [
     ("fotg_upsample_crop_color", C.c_int, [vp, C.c_int, vp, C.c_float, vp, vp, vp]),
     ("fotg_fb_check", C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp]),
     ("fotg_upsample_crop_fb_check", C.c_int, [vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]),
+    ("fotg_warp", C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
+    ("fotg_warp_u8", C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_warp", C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_warp_u8", C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
     ("fotg_level_size", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_out_size", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_num_patches", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -246,6 +246,11 @@ class OFClass:
         from .consistency import upsample_crop_fb_check
         return upsample_crop_fb_check(self, flow, flow_bw, alpha1=alpha1, alpha2=alpha2, stats=stats, fused=fused)
 
+    def upsample_crop_warp(self, flow, src, ref=None, occ=None, fill=None, stats=False, fused=True):
+        """src pulled back along upsample_crop(flow), with validity codes and photometric residuals -- flowonthego_amd.warp"""
+        from .warp import upsample_crop_warp
+        return upsample_crop_warp(self, flow, src, ref=ref, occ=occ, fill=fill, stats=stats, fused=fused)
+
     # -- pyramid (src/oflow.cpp:182-207 ConstructImgPyramids) -----------------------------------------------
     def ConstructImgPyramids(self, I0, I1):
         n = I0.shape[0]

@@ -285,6 +285,51 @@ int fotg_fb_check(int device, int n, const float *flow, const float *flow_bw, in
 int fotg_upsample_crop_fb_check(fotg_ctx *ctx, int n, const float *flow, const float *flow_bw, float alpha1, float alpha2,
                                 unsigned char *mask, unsigned char *mask_bw, unsigned *counts, void *stream);
 
+/* ---- warp an image along a flow (the reference's image_warp, kroeger/FDF1.0.1/opticalflow_aux.c:18-60), csrc/warp.hip.h -------
+ * Per pixel (x, y) of a w x h image, channel c, all arithmetic f32, every operation rounded on its own, in this order:
+ *   u, v = F[y][x]
+ *   if !isfinite(u) || !isfinite(v):            own = 3; value = fill            (the reference converts NaN to int: undefined)
+ *   xx = (float)x + u;  yy = (float)y + v
+ *   fx = floorf(xx);    fy = floorf(yy)         (== (float)(int)floor(xx) wherever the reference's conversion is defined)
+ *   dx = xx - fx;       dy = yy - fy
+ *   own = (xx >= 0 && xx <= w-1 && yy >= 0 && yy <= h-1) ? 0 : 2                 (image_warp's mask == (own == 0))
+ *   xi = fx saturated to [-2, w] as int, yi alike to [-2, h]                     (x + 1 cannot overflow)
+ *   x1 = clamp(xi, 0, w-1); x2 = clamp(xi+1, 0, w-1); y1, y2 alike
+ *   value_c = S[y1][x1][c]*(1-dx)*(1-dy) + S[y1][x2][c]*dx*(1-dy) + S[y2][x1][c]*(1-dx)*dy + S[y2][x2][c]*dx*dy
+ *                                                                                (four products summed left to right)
+ *   code = own != 0 ? own : (occ ? occ[y][x] (0, 1 or 3; 2 cannot differ from own) : 0)
+ *   fill_mode 0 (reference): dst = value wherever own != 3
+ *   fill_mode 1:             dst = code == 0 ? value : fill
+ * src (S): the image to warp (frame 1 for a forward flow), n x h x w x channels interleaved, channels 1 or 3, f32 (fotg_warp) or
+ * 8-bit (fotg_warp_u8), on the device; flow: n x h x w x 2 f32.  8-bit taps are converted exactly to f32; an 8-bit dst is
+ * rintf(value) clamped to [0, 255] (and fill likewise, a NaN becoming 0); the residuals below use the unrounded f32 value.  With
+ * fill_mode 0, occ NULL and a finite flow, dst and code == 0 are the reference's dst and mask, bit for bit, for any finite flow
+ * however large.  occ: NULL or n x h x w uint8, a mask of fotg_fb_check (a byte above 3 counts as 3).  To warp frame 0 onto
+ * frame 1's grid pass frame 0 as src, the backward flow and mask_bw.
+ * Outputs, each may be NULL (not all three): dst, of src's layout and type (it must not overlap src); code: n x h x w uint8, the
+ * alphabet of fotg_fb_check; stats: n x 6 f64 per image: [0..3] the pixels of code 0, 1, 2, 3 and, when a comparison image ref
+ * (frame 0; src's layout and type) is given, over the code-0 pixels and all channels [4] sum (double)|ref - value| and
+ * [5] sum (double)|ref - S[y][x]| (the unwarped difference at the same pixels), every term the f32 fabsf of the f32 difference;
+ * without ref both are 0.  The sums are added in a fixed order (no floating-point atomics): the same bits every run, and the
+ * same from the dense and the fused form.  Asynchronous on `stream`; the partial sums live in stream-ordered memory of the call.
+ * FOTG_ERR_ARG: n < 1 (or > 65535), w or h <= 0, channels not 1 or 3, fill_mode not 0 or 1, a null src or flow, all three
+ * outputs null, dst overlapping src. */
+int fotg_warp(int device, int n, const float *src, const float *flow, int w, int h, int channels, const float *ref,
+              const unsigned char *occ, int fill_mode, float fill, float *dst, unsigned char *code, double *stats, void *stream);
+int fotg_warp_u8(int device, int n, const unsigned char *src, const float *flow, int w, int h, int channels,
+                 const unsigned char *ref, const unsigned char *occ, int fill_mode, float fill, unsigned char *dst,
+                 unsigned char *code, double *stats, void *stream);
+/* The same along the coarse flow of a context (n x hl x wl x 2, the layout of fotg_calc_batch's outflow), upsampled and cropped on
+ * the fly: images of h_org x w_org; every output equals fotg_warp(fotg_upsample_crop(coarse_flow)) bit for bit, the six
+ * statistics included, without writing the full-resolution flow.  channels is explicit because a gray context may be fed
+ * three-channel frames (u8_color).  FOTG_ERR_ARG also for n > max_batch and a depth-mode context. */
+int fotg_upsample_crop_warp(fotg_ctx *ctx, int n, const float *coarse_flow, const float *src, int channels, const float *ref,
+                            const unsigned char *occ, int fill_mode, float fill, float *dst, unsigned char *code, double *stats,
+                            void *stream);
+int fotg_upsample_crop_warp_u8(fotg_ctx *ctx, int n, const float *coarse_flow, const unsigned char *src, int channels,
+                               const unsigned char *ref, const unsigned char *occ, int fill_mode, float fill, unsigned char *dst,
+                               unsigned char *code, double *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
