@@ -30,6 +30,7 @@ struct CtxUpsampleGeom {
   int wl, hl;        // coarse flow size (the padded frame >> sc_l)
   int x0, y0;        // crop offsets: padw / 2, padh / 2
   int w_org, h_org;
+  int bidir;         // created with fotg_params::bidir
 };
 int ctx_upsample_geom(const fotg_ctx *c, CtxUpsampleGeom *g);
 void set_last_hip_error(int e);

@@ -162,7 +162,7 @@ int ctx_upsample_geom(const fotg_ctx *c, CtxUpsampleGeom *g)
 {
   if (!c || !g) return FOTG_ERR_ARG;
   const LevelGeom &l = c->geom[c->p.sc_l];
-  *g = {c->device, c->max_batch, c->nch, c->p.sc_l, l.w, l.h, c->padw / 2, c->padh / 2, c->w_org, c->h_org};
+  *g = {c->device, c->max_batch, c->nch, c->p.sc_l, l.w, l.h, c->padw / 2, c->padh / 2, c->w_org, c->h_org, c->p.bidir};
   return FOTG_OK;
 }
 void set_last_hip_error(int e) { g_last_hip = e; }

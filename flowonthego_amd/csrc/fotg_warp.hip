@@ -3,9 +3,16 @@
 // folds the per-workgroup partials (stream-ordered memory of the call) into them.  Asynchronous on the caller's stream; no host
 // synchronisation.
 #include "common.h"
+#define FOTG_WARP_FOLD_KERNEL
 #include "warp.hip.h"
 
 using namespace fotg;
+
+hipError_t fotg::warp_fold(const WarpPartial *part, int blocks, int n, double *stats, hipStream_t stream)
+{
+  warp_fold_kernel<<<dim3((unsigned)n), WARP_THREADS, 0, stream>>>(part, blocks, stats);
+  return hipGetLastError();
+}
 
 namespace {
 
@@ -60,8 +67,7 @@ int warp_batch(int device, int n, const Src &flow, const T *src, int w, int h, i
   hipError_t e = hipGetLastError();
   if (stats) {
     if (e == hipSuccess) {
-      warp_fold_kernel<<<dim3((unsigned)n), WARP_THREADS, 0, stream>>>(part, (int)blocks, stats);
-      e = hipGetLastError();
+      e = warp_fold(part, (int)blocks, n, stats, stream);
     }
     const hipError_t ef = hipFreeAsync(part, stream);
     if (e == hipSuccess) e = ef;

@@ -92,6 +92,94 @@ __device__ __forceinline__ int warp_sat(float f, int n)      // f saturated to [
   return f < -2.f ? -2 : (f > (float)n ? n : (int)f);
 }
 
+// image_warp's mask: the sample position lies inside the frame
+__device__ __forceinline__ bool warp_inside(float xx, float yy, int w, int h)
+{
+  return xx >= 0.f && xx <= (float)(w - 1) && yy >= 0.f && yy <= (float)(h - 1);
+}
+
+// the value of image S (w x h x NOC) at (xx, yy): the four clamped taps of the head of this file, in its order.  Shared with
+// interp.hip.h, whose costs and samples are this arithmetic.
+template <class T, int NOC>
+__device__ __forceinline__ void warp_taps(const T *__restrict__ S, int w, int h, float xx, float yy, float (&value)[NOC])
+{
+  const float fx = floorf(xx), fy = floorf(yy);
+  const float dx = xx - fx, dy = yy - fy;
+  const int xi = warp_sat(fx, w), yi = warp_sat(fy, h);
+  const int x1 = clampi(xi, w), x2 = clampi(xi + 1, w), y1 = clampi(yi, h), y2 = clampi(yi + 1, h);
+  const size_t a11 = ((size_t)y1 * w + x1) * NOC, a12 = ((size_t)y1 * w + x2) * NOC;
+  const size_t a21 = ((size_t)y2 * w + x1) * NOC, a22 = ((size_t)y2 * w + x2) * NOC;
+#pragma unroll
+  for (int c = 0; c < NOC; ++c)
+    value[c] = warp_elem(S, a11 + c) * (1.0f - dx) * (1.0f - dy) + warp_elem(S, a12 + c) * dx * (1.0f - dy) +
+               warp_elem(S, a21 + c) * (1.0f - dx) * dy + warp_elem(S, a22 + c) * dx * dy;
+}
+
+// the thread's nb (<= 4) pixels val[4 NOC] to o: 16-byte / dword nontemporal stores where the span is whole and aligned
+template <class T, int NOC>
+__device__ __forceinline__ void warp_store4(T *__restrict__ o, const float (&val)[4 * NOC], int nb)
+{
+  typedef float vf4 __attribute__((ext_vector_type(4)));
+  if constexpr (sizeof(T) == 4) {
+    if (nb == 4 && (((size_t)o) & 15) == 0) {
+#pragma unroll
+      for (int k = 0; k < NOC; ++k)
+        __builtin_nontemporal_store(vf4{val[4 * k], val[4 * k + 1], val[4 * k + 2], val[4 * k + 3]}, reinterpret_cast<vf4 *>(o) + k);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4 * NOC; ++k)
+        if (k < nb * NOC) o[k] = val[k];
+    }
+  } else {
+    unsigned b[4 * NOC];
+#pragma unroll
+    for (int k = 0; k < 4 * NOC; ++k) b[k] = warp_to_u8(val[k]);
+    if (nb == 4 && (((size_t)o) & 3) == 0) {
+#pragma unroll
+      for (int k = 0; k < NOC; ++k)
+        __builtin_nontemporal_store(b[4 * k] | b[4 * k + 1] << 8 | b[4 * k + 2] << 16 | b[4 * k + 3] << 24, reinterpret_cast<unsigned *>(o) + k);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4 * NOC; ++k)
+        if (k < nb * NOC) o[k] = (unsigned char)b[k];
+    }
+  }
+}
+
+// the thread's nb (<= 4) code bytes, packed in word, to o
+__device__ __forceinline__ void warp_store_code4(unsigned char *__restrict__ o, unsigned word, int nb)
+{
+  if (nb == 4 && (((size_t)o) & 3) == 0) {
+    __builtin_nontemporal_store(word, reinterpret_cast<unsigned *>(o));
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < nb) o[i] = (unsigned char)(word >> (8 * i));
+  }
+}
+
+// the workgroup's statistics in the fixed order of the head of this file (wave: xor shuffles 32 .. 1; workgroup: waves in index
+// order through LDS) into *out.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void warp_block_reduce(unsigned c01, unsigned c23, double s0, double s1, WarpPartial *__restrict__ out)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    c01 += __shfl_xor(c01, o, 64); c23 += __shfl_xor(c23, o, 64);
+    s0 += __shfl_xor(s0, o, 64); s1 += __shfl_xor(s1, o, 64);
+  }
+  __shared__ WarpPartial wp[WARP_THREADS / FOTG_WAVE];
+  const int wave = threadIdx.x / FOTG_WAVE, lane = threadIdx.x % FOTG_WAVE;
+  if (lane == 0) { wp[wave].s[0] = s0; wp[wave].s[1] = s1; wp[wave].c01 = c01; wp[wave].c23 = c23; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    WarpPartial t = wp[0];
+    for (int i = 1; i < WARP_THREADS / FOTG_WAVE; ++i) {
+      t.s[0] += wp[i].s[0]; t.s[1] += wp[i].s[1]; t.c01 += wp[i].c01; t.c23 += wp[i].c23;
+    }
+    *out = t;
+  }
+}
+
 // flow: the vectors; src / ref / dst: n x h x w x NOC of T (ref, dst may be null); occ / code: n x h x w bytes or null;
 // part: (n x gridDim.x) WarpPartial or null.
 template <class Src, class T, int NOC>
@@ -100,7 +188,6 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_kernel(Src flow, const T *_
                                                             float fill, T *__restrict__ dst, unsigned char *__restrict__ code,
                                                             WarpPartial *__restrict__ part)
 {
-  typedef float vf4 __attribute__((ext_vector_type(4)));
   const int pair = blockIdx.y;
   const long hw = (long)w * h, base = (long)pair * hw;
   const long r0 = 4 * ((long)blockIdx.x * blockDim.x + threadIdx.x);
@@ -137,19 +224,8 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_kernel(Src flow, const T *_
         for (int c = 0; c < NOC; ++c) value[c] = fill;
         if (__builtin_isfinite(u[i]) && __builtin_isfinite(v[i])) {
           const float xx = (float)x + u[i], yy = (float)y + v[i];
-          const float fx = floorf(xx), fy = floorf(yy);
-          const float dx = xx - fx, dy = yy - fy;
-          own = (xx >= 0.f && xx <= (float)(w - 1) && yy >= 0.f && yy <= (float)(h - 1)) ? 0u : 2u;
-          if (want_value) {
-            const int xi = warp_sat(fx, w), yi = warp_sat(fy, h);
-            const int x1 = clampi(xi, w), x2 = clampi(xi + 1, w), y1 = clampi(yi, h), y2 = clampi(yi + 1, h);
-            const size_t a11 = ((size_t)y1 * w + x1) * NOC, a12 = ((size_t)y1 * w + x2) * NOC;
-            const size_t a21 = ((size_t)y2 * w + x1) * NOC, a22 = ((size_t)y2 * w + x2) * NOC;
-#pragma unroll
-            for (int c = 0; c < NOC; ++c)
-              value[c] = warp_elem(S, a11 + c) * (1.0f - dx) * (1.0f - dy) + warp_elem(S, a12 + c) * dx * (1.0f - dy) +
-                         warp_elem(S, a21 + c) * (1.0f - dx) * dy + warp_elem(S, a22 + c) * dx * dy;
-          }
+          own = warp_inside(xx, yy, w, h) ? 0u : 2u;
+          if (want_value) warp_taps<T, NOC>(S, w, h, xx, yy, value);
         }
         unsigned cd = own;
         if (own == 0 && occ) {
@@ -176,63 +252,17 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_kernel(Src flow, const T *_
       }
       if (++x == w) { x = 0; ++y; }
     }
-    if (dst) {
-      T *o = dst + (size_t)(base + r0) * NOC;
-      if constexpr (sizeof(T) == 4) {
-        if (nb == 4 && (((size_t)o) & 15) == 0) {
-#pragma unroll
-          for (int k = 0; k < NOC; ++k)
-            __builtin_nontemporal_store(vf4{val[4 * k], val[4 * k + 1], val[4 * k + 2], val[4 * k + 3]}, reinterpret_cast<vf4 *>(o) + k);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4 * NOC; ++k)
-            if (k < nb * NOC) o[k] = val[k];
-        }
-      } else {
-        unsigned b[4 * NOC];
-#pragma unroll
-        for (int k = 0; k < 4 * NOC; ++k) b[k] = warp_to_u8(val[k]);
-        if (nb == 4 && (((size_t)o) & 3) == 0) {
-#pragma unroll
-          for (int k = 0; k < NOC; ++k)
-            __builtin_nontemporal_store(b[4 * k] | b[4 * k + 1] << 8 | b[4 * k + 2] << 16 | b[4 * k + 3] << 24, reinterpret_cast<unsigned *>(o) + k);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4 * NOC; ++k)
-            if (k < nb * NOC) o[k] = (unsigned char)b[k];
-        }
-      }
-    }
-    if (code) {
-      unsigned char *o = code + (size_t)base + (size_t)r0;
-      if (nb == 4 && (((size_t)o) & 3) == 0) {
-        __builtin_nontemporal_store(word, reinterpret_cast<unsigned *>(o));
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (i < nb) o[i] = (unsigned char)(word >> (8 * i));
-      }
-    }
+    if (dst) warp_store4<T, NOC>(dst + (size_t)(base + r0) * NOC, val, nb);
+    if (code) warp_store_code4(code + (size_t)base + (size_t)r0, word, nb);
   }
-  if (!part) return;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    c01 += __shfl_xor(c01, o, 64); c23 += __shfl_xor(c23, o, 64);
-    s_warp += __shfl_xor(s_warp, o, 64); s_unw += __shfl_xor(s_unw, o, 64);
-  }
-  __shared__ WarpPartial wp[WARP_THREADS / FOTG_WAVE];
-  const int wave = threadIdx.x / FOTG_WAVE, lane = threadIdx.x % FOTG_WAVE;
-  if (lane == 0) { wp[wave].s[0] = s_warp; wp[wave].s[1] = s_unw; wp[wave].c01 = c01; wp[wave].c23 = c23; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    WarpPartial t = wp[0];
-    for (int i = 1; i < WARP_THREADS / FOTG_WAVE; ++i) {
-      t.s[0] += wp[i].s[0]; t.s[1] += wp[i].s[1]; t.c01 += wp[i].c01; t.c23 += wp[i].c23;
-    }
-    part[(size_t)pair * gridDim.x + blockIdx.x] = t;
-  }
+  if (part) warp_block_reduce(c01, c23, s_warp, s_unw, part + (size_t)pair * gridDim.x + blockIdx.x);
 }
 
+// launches warp_fold_kernel for n images on `stream` (defined in fotg_warp.hip, the one translation unit that compiles the kernel;
+// fotg_interp.hip folds its partials through it too)
+hipError_t warp_fold(const WarpPartial *part, int blocks, int n, double *stats, hipStream_t stream);
+
+#ifdef FOTG_WARP_FOLD_KERNEL
 // grid n, 256 threads: the `blocks` partials of image blockIdx.x, added in a fixed order, into stats[6 blockIdx.x ..]
 __global__ __launch_bounds__(WARP_THREADS) void warp_fold_kernel(const WarpPartial *__restrict__ part, int blocks, double *__restrict__ stats)
 {
@@ -268,5 +298,6 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_fold_kernel(const WarpParti
     stats[(size_t)blockIdx.x * WARP_NSTAT + k] = r;
   }
 }
+#endif  // FOTG_WARP_FOLD_KERNEL
 
 }  // namespace fotg

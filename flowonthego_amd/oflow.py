@@ -251,6 +251,25 @@ class OFClass:
         from .warp import upsample_crop_warp
         return upsample_crop_warp(self, flow, src, ref=ref, occ=occ, fill=fill, stats=stats, fused=fused)
 
+    def bidirectional_flows(self, I0, I1):
+        """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
+        upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""
+        u8 = isinstance(I0, torch.Tensor) and I0.dtype == torch.uint8
+        return self.calc_bidirectional_u8(I0, I1) if u8 else self.calc_bidirectional(I0, I1)
+
+    def upsample_crop_interpolate(self, flow, flow_bw, I0, I1, t, mask_fw=None, mask_bw=None, ref=None, stats=False, alpha1=0.01,
+                                  alpha2=0.5, fused=True):
+        """the frame at time t between I0 and I1 from upsample_crop(flow) / upsample_crop(flow_bw) -- flowonthego_amd.interp"""
+        from .interp import upsample_crop_interpolate
+        return upsample_crop_interpolate(self, flow, flow_bw, I0, I1, t, mask_fw=mask_fw, mask_bw=mask_bw, ref=ref, stats=stats,
+                                         alpha1=alpha1, alpha2=alpha2, fused=fused)
+
+    def interpolate(self, I0, I1, t, ref=None, stats=False, alpha1=0.01, alpha2=0.5, fused=True):
+        """the frame(s) at time t (or at every t of a sequence) between I0 and I1: both flows from one pyramid per frame, the
+        consistency check and the interpolation -- flowonthego_amd.interp.  Needs opt_params.bidir."""
+        from .interp import flow_and_interpolate
+        return flow_and_interpolate(self, I0, I1, t, ref=ref, stats=stats, alpha1=alpha1, alpha2=alpha2, fused=fused)
+
     # -- pyramid (src/oflow.cpp:182-207 ConstructImgPyramids) -----------------------------------------------
     def ConstructImgPyramids(self, I0, I1):
         n = I0.shape[0]

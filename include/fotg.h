@@ -330,6 +330,65 @@ int fotg_upsample_crop_warp_u8(fotg_ctx *ctx, int n, const float *coarse_flow, c
                                const unsigned char *ref, const unsigned char *occ, int fill_mode, float fill, unsigned char *dst,
                                unsigned char *code, double *stats, void *stream);
 
+/* ---- the frame at time t between two frames, from their bidirectional flow, csrc/interp.hip.h ---------------------------------
+ * The interpolation procedure of the Middlebury flow benchmark (Baker et al., "A Database and Evaluation Methodology for Optical
+ * Flow", section 3.3).  I0, I1: w x h frames; F (0 -> 1), B (1 -> 0): full-resolution flows; mF, mB: their masks in
+ * fotg_fb_check's alphabet; 0 < t < 1; t1 = 1.0f - t.  All arithmetic f32, every operation rounded on its own, in this order;
+ * taps(S, xx, yy) and inside(xx, yy) are fotg_warp's value_c (four clamped taps) and its in-frame test (own == 0).
+ * 1. Candidates, per direction: forward (Isrc, Idst, V, m, s) = (I0, I1, F, mF, t), backward = (I1, I0, B, mB, t1).
+ *    Per source pixel p = (x, y), linear index i = y w + x:
+ *      u, v = V[p];  skip unless isfinite(u) && isfinite(v)
+ *      c = m[p];     skip unless c <= 1                                   (codes 2 and 3, and any byte above, never project)
+ *      val = taps(Idst, (float)x + u, (float)y + v)
+ *      e = the sum over the channels, in order, of fabsf(Isrc[p][ch] - val[ch])        (fotg_warp's residual term)
+ *      q = e * 256 < 16777215 ? (unsigned)floorf(e * 256) : 16777215                   (a NaN cost is the largest)
+ *      tx = floorf(((float)x + s * u) + 0.5f);  ty alike;  skip unless 0 <= tx <= w-1 && 0 <= ty <= h-1
+ *      key = (uint64)c << 56 | (uint64)q << 32 | i                                     (hence w h < 2^32)
+ *      K[ty][tx] = min(K[ty][tx], key)                  (K starts as all ones = empty; one 64-bit integer atomic min)
+ *    A consistent candidate beats an inconsistent one, then the lower cost wins, then the lower source index.  A minimum does not
+ *    depend on the order of arrival: the result is deterministic by construction.
+ * 2. Resolve, per target pixel (x, y):
+ *      a forward key:        p* = its low 32 bits, (Vu, Vv) = F[p*],  origin 0
+ *      else a backward key:  p* likewise,          (Vu, Vv) = -B[p*], origin 1
+ *      else:                                       (Vu, Vv) = 0,      origin 2 (a hole)
+ *      x0 = (float)x - t * Vu;  y0 alike;  x1 = (float)x + t1 * Vu;  y1 alike
+ *      v0 = taps(I0, x0, y0);  in0 = inside(x0, y0);  v1 = taps(I1, x1, y1);  in1 = inside(x1, y1)
+ *      o0 = mF[clamp(floorf(y0 + 0.5f), 0, h-1)][clamp(floorf(x0 + 0.5f), 0, w-1)] != 0;  o1 alike from mB at (x1, y1)
+ *      use0 = in0;  use1 = in1;  for origin != 2:  if (o1 && !o0) use0 = false;  if (o0 && !o1) use1 = false
+ *      value = use0 && !use1 ? v0 : use1 && !use0 ? v1 : t1 * v0 + t * v1
+ *    -- the weighted mean (w0 v0 + w1 v1) / (w0 + w1) with w0 = use0 ? t1 : 0 and w1 = use1 ? t : 0, or the plain blend when both
+ *    are 0, written without the division (the weights sum to t1, t or t1 + t).
+ *      an 8-bit dst is rounded as fotg_warp's;  code = origin + 4 (use0 && !use1) + 8 (use1 && !use0)
+ * 3. stats, per image six doubles: [0..2] the pixels of origin 0, 1, 2; [3] the one-sided pixels (code >= 4); with a comparison
+ *    frame ref (the true frame at t, I0's layout and type) over all pixels and channels [4] sum (double)|ref - value| and
+ *    [5] sum (double)|ref - (t1 * I0[y][x] + t * I1[y][x])| (the plain blend), each term the f32 fabsf of the f32 difference of the
+ *    unrounded value; without ref both are 0.  Added in fotg_warp's fixed order: the same bits every run and from both forms.
+ * I0, I1, ref, dst: n x h x w x channels interleaved, channels 1 or 3, f32 (fotg_interp) or 8-bit (fotg_interp_u8), on the device;
+ * flow_fw, flow_bw: n x h x w x 2 f32; mask_fw, mask_bw: n x h x w uint8, both given (e.g. fotg_fb_check's) or both NULL: the call
+ * then runs fotg_fb_check's kernel with alpha1, alpha2 into memory of its own (ignored when the masks are given).
+ * Outputs, each may be NULL (not all three): dst (it must not overlap I0 or I1), code (n x h x w uint8), stats (n x 6 f64).
+ * Asynchronous on `stream`.  Key planes (16 bytes per pixel), the call's own masks and the partial sums live in stream-ordered
+ * memory of the call; a batch is processed in chunks of as many images as 256 MiB of key planes hold.
+ * FOTG_ERR_ARG: n < 1 (or > 65535), w or h <= 0, w h >= 2^32, channels not 1 or 3, t not inside (0, 1), a null frame or flow,
+ * one mask without the other, all three outputs null, dst overlapping a frame. */
+int fotg_interp(int device, int n, const float *I0, const float *I1, const float *flow_fw, const float *flow_bw, int w, int h,
+                int channels, float t, const unsigned char *mask_fw, const unsigned char *mask_bw, float alpha1, float alpha2,
+                const float *ref, float *dst, unsigned char *code, double *stats, void *stream);
+int fotg_interp_u8(int device, int n, const unsigned char *I0, const unsigned char *I1, const float *flow_fw, const float *flow_bw,
+                   int w, int h, int channels, float t, const unsigned char *mask_fw, const unsigned char *mask_bw, float alpha1,
+                   float alpha2, const unsigned char *ref, unsigned char *dst, unsigned char *code, double *stats, void *stream);
+/* The same from the coarse flows of a bidirectional context (n x hl x wl x 2 each, the outflows of fotg_calc_bidir), upsampled and
+ * cropped on the fly, frames of h_org x w_org: every output equals fotg_interp on fotg_upsample_crop's outputs (and, with NULL
+ * masks, fotg_fb_check's masks of them) byte for byte, the statistics included, without writing a full-resolution flow.
+ * FOTG_ERR_UNSUPPORTED: a context created without fotg_params::bidir.  FOTG_ERR_ARG also for n > max_batch. */
+int fotg_upsample_crop_interp(fotg_ctx *ctx, int n, const float *coarse_fw, const float *coarse_bw, const float *I0, const float *I1,
+                              int channels, float t, const unsigned char *mask_fw, const unsigned char *mask_bw, float alpha1,
+                              float alpha2, const float *ref, float *dst, unsigned char *code, double *stats, void *stream);
+int fotg_upsample_crop_interp_u8(fotg_ctx *ctx, int n, const float *coarse_fw, const float *coarse_bw, const unsigned char *I0,
+                                 const unsigned char *I1, int channels, float t, const unsigned char *mask_fw,
+                                 const unsigned char *mask_bw, float alpha1, float alpha2, const unsigned char *ref,
+                                 unsigned char *dst, unsigned char *code, double *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
