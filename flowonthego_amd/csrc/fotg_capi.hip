@@ -10,6 +10,7 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include "common.h"
 #include "pipe_tickets.h"
 #include "pyramid.hip.h"
@@ -51,12 +52,22 @@ struct DevGuard {
   DevGuard dev_guard_(dev);                                                         \
   if (!dev_guard_.ok) { g_last_hip = (int)hipGetLastError(); return FOTG_ERR_HIP; }
 
-struct GridState {
-  const float *I0 = nullptr, *I0x = nullptr, *I0y = nullptr, *I1 = nullptr;
-  long stride = 0;
-  const float *flow_prev = nullptr;
-  float *trace_host = nullptr;
-  int camlr = 0;                     // depth mode: camera side of this grid (kroeger/oflow.cpp:153,157)
+struct GridState {                   // (zero with the context: fotg_create)
+  const float *I0, *I0x, *I0y, *I1;
+  long stride;
+  const float *flow_prev;
+  float *trace_host;
+  int camlr;                         // depth mode: camera side of this grid (kroeger/oflow.cpp:153,157)
+};
+// one patch grid = one flow direction: per level what LK writes and the densification reads, and the inputs of its next LK launch
+struct Grid {
+  float *p_iter[FOTG_MAXLEV];        // [B][nop][2]
+  float *pweight[FOTG_MAXLEV];       // [B][nop][nv]
+  GridState gs[FOTG_MAXLEV];
+};
+// where a frame's pyramid goes: per level the padded image [B][th][tw][noc] and, of a template-type pyramid, its gradients
+struct PyrBufs {
+  float *im[FOTG_MAXLEV], *dx[FOTG_MAXLEV], *dy[FOTG_MAXLEV];
 };
 
 // Switches read ONCE from the environment at fotg_create (tests force the kernel variants through them; nothing under
@@ -99,14 +110,13 @@ struct fotg_ctx {
   int nch;                           // flow channels: 2, or 1 in stereo depth mode (op.nop, kroeger/oflow.cpp:76-80)
   int base_lv;                       // first level the pyramid materialises: min(sc_l, 4)
   LevelGeom geom[FOTG_MAXLEV];
-  float *im[2][FOTG_MAXLEV];         // padded level images  [B][th][tw][noc]
-  float *dx0[FOTG_MAXLEV], *dy0[FOTG_MAXLEV];
+  PyrBufs pyr[2];                    // frame 0 (sequence mode: every frame) and frame 1; frame 1 has gradients only with usefbcon / bidir
   long lev_stride[FOTG_MAXLEV];      // floats per pair in a level buffer
   float *flow[FOTG_MAXLEV];          // [B][h][w][2]
-  float *p_iter[FOTG_MAXLEV];        // [B][nop][2]
-  float *pweight[FOTG_MAXLEV];       // [B][nop][nv]
-  // forward-backward merge (usefbcon): frame-1 gradients and the backward grid / flow (kroeger/oflow.cpp:133-170)
-  float *dx1[FOTG_MAXLEV], *dy1[FOTG_MAXLEV], *p_iter_bw[FOTG_MAXLEV], *pweight_bw[FOTG_MAXLEV], *flow_bw[FOTG_MAXLEV];
+  Grid fw;
+  // forward-backward merge (usefbcon) and bidir: the backward grid / flow (kroeger/oflow.cpp:133-170)
+  Grid bw;
+  float *flow_bw[FOTG_MAXLEV];
   float *tap_t[FOTG_MAXLEV], *tap_tx[FOTG_MAXLEV], *tap_ty[FOTG_MAXLEV], *tap_hes[FOTG_MAXLEV];
   int *tap_cnt[FOTG_MAXLEV];
   float *trace_dev[FOTG_MAXLEV];
@@ -134,7 +144,6 @@ struct fotg_ctx {
   int *stall_host, *stall_dev;
   long stalls;                       // host-side count of the times the word was found set
   unsigned long long *stamps;        // -DFOTG_TILE_STATS builds only
-  GridState gs[FOTG_MAXLEV];
 };
 
 static void fill_geom(const fotg_params &p, int Wp, int Hp, int l, LevelGeom &g)
@@ -229,9 +238,9 @@ void fotg_destroy(fotg_ctx *c)
   if (c->nguards > 0) (void)fotg_ctx_counter(c, "guard_violations");      // (prints what it finds)
 #endif
   for (int l = 0; l < FOTG_MAXLEV; ++l) {
-    (void)hipFree(c->im[0][l]); (void)hipFree(c->im[1][l]); (void)hipFree(c->dx0[l]); (void)hipFree(c->dy0[l]);
-    (void)hipFree(c->flow[l]); (void)hipFree(c->p_iter[l]); (void)hipFree(c->pweight[l]);
-    (void)hipFree(c->dx1[l]); (void)hipFree(c->dy1[l]); (void)hipFree(c->p_iter_bw[l]); (void)hipFree(c->pweight_bw[l]); (void)hipFree(c->flow_bw[l]);
+    for (PyrBufs &f : c->pyr) { (void)hipFree(f.im[l]); (void)hipFree(f.dx[l]); (void)hipFree(f.dy[l]); }
+    for (Grid *g : {&c->fw, &c->bw}) { (void)hipFree(g->p_iter[l]); (void)hipFree(g->pweight[l]); }
+    (void)hipFree(c->flow[l]); (void)hipFree(c->flow_bw[l]);
     (void)hipFree(c->tap_t[l]); (void)hipFree(c->tap_tx[l]); (void)hipFree(c->tap_ty[l]); (void)hipFree(c->tap_hes[l]); (void)hipFree(c->tap_cnt[l]);
     (void)hipFree(c->trace_dev[l]);
     (void)hipFree(c->vrC[l]); (void)hipFree(c->vrD[l]); (void)hipFree(c->vrX[l]);
@@ -302,20 +311,20 @@ int fotg_create(const fotg_params *p, int w_org, int h_org, int device, int max_
 #define ALLOC(ptr, nbytes) do { if (hipMalloc((void **)&(ptr), (nbytes)) != hipSuccess) { g_last_hip = (int)hipGetLastError(); fotg_destroy(c); return FOTG_ERR_HIP; } } while (0)
 #endif
     const size_t bytes1 = (B + 1) * c->lev_stride[l] * sizeof(float);       // sequence mode: max_batch pairs = max_batch + 1 frames
-    ALLOC(c->im[0][l], bytes1);
-    ALLOC(c->im[1][l], bytes);
+    ALLOC(c->pyr[0].im[l], bytes1);
+    ALLOC(c->pyr[1].im[l], bytes);
     if (l >= p->sc_l) {
-      ALLOC(c->dx0[l], bytes1);
-      ALLOC(c->dy0[l], bytes1);
+      ALLOC(c->pyr[0].dx[l], bytes1);
+      ALLOC(c->pyr[0].dy[l], bytes1);
       ALLOC(c->flow[l], B * g.w * g.h * 2 * sizeof(float));
-      ALLOC(c->p_iter[l], B * g.nop * 2 * sizeof(float));
-      ALLOC(c->pweight[l], B * g.nop * (size_t)(p->ps * p->ps * c->noc) * sizeof(float));
+      ALLOC(c->fw.p_iter[l], B * g.nop * 2 * sizeof(float));
+      ALLOC(c->fw.pweight[l], B * g.nop * (size_t)(p->ps * p->ps * c->noc) * sizeof(float));
       if (p->usefbcon || p->bidir) {
-        ALLOC(c->dx1[l], bytes);
-        ALLOC(c->dy1[l], bytes);
+        ALLOC(c->pyr[1].dx[l], bytes);
+        ALLOC(c->pyr[1].dy[l], bytes);
         ALLOC(c->flow_bw[l], B * g.w * g.h * 2 * sizeof(float));
-        ALLOC(c->p_iter_bw[l], B * g.nop * 2 * sizeof(float));
-        ALLOC(c->pweight_bw[l], B * g.nop * (size_t)(p->ps * p->ps * c->noc) * sizeof(float));
+        ALLOC(c->bw.p_iter[l], B * g.nop * 2 * sizeof(float));
+        ALLOC(c->bw.pweight[l], B * g.nop * (size_t)(p->ps * p->ps * c->noc) * sizeof(float));
       }
     }
   }
@@ -418,10 +427,11 @@ int fotg_num_patches(const fotg_ctx *c, int l, int *nopw, int *noph)
 /* pyramid                                                                                          */
 /* ------------------------------------------------------------------------------------------------ */
 }  // extern "C"
-// I0 and/or I1 may be given; both frames of a batch share the launches
+// I0 and/or I1 may be given; both frames of a batch share the launches.  I0's pyramid (template type: with gradients) goes to d0,
+// I1's (target type: the images only) to d1.
 // SRCC: channels of the source frames (3 with NOC = 1: 8-bit colour frames, gray on load -- fotg_params::u8_color)
 template <int NOC, typename T = float, int SRCC = NOC>
-static int pyramid_impl(fotg_ctx *c, int n, const T *I0, const T *I1, hipStream_t s, int stages = 3)
+static int pyramid_impl(fotg_ctx *c, int n, const T *I0, const T *I1, const PyrBufs &d0, const PyrBufs &d1, hipStream_t s, int stages = 3)
 {
   const int lv = c->base_lv, ps = c->ps;
   const LevelGeom &g0 = c->geom[lv];
@@ -429,7 +439,7 @@ static int pyramid_impl(fotg_ctx *c, int n, const T *I0, const T *I1, hipStream_
   const long fstride = (long)c->w_org * c->h_org * SRCC;
   const int coef0 = c->p.u8_color == 2 ? 4899 : 1868, coef2 = c->p.u8_color == 2 ? 1868 : 4899;      // first / third byte of a pixel: B, R (cv::imread order) or R, B
   const T *A = I0 ? I0 : I1, *B = (I0 && I1) ? I1 : nullptr;
-  float *dA = c->im[I0 ? 0 : 1][lv], *dB = c->im[1][lv];
+  float *dA = (I0 ? d0 : d1).im[lv], *dB = d1.im[lv];
   const int nimg = B ? 2 * n : n;
   // fast path: no horizontal padding, rows and frames aligned for the wide loads (16 B for f32, 4 B for u8)
   const uintptr_t amask = sizeof(T) == 4 ? 15 : 3;
@@ -476,7 +486,7 @@ static int pyramid_impl(fotg_ctx *c, int n, const T *I0, const T *I1, hipStream_
     memset(&fa, 0, sizeof(fa));
     for (int k = 0; k < nlev; ++k) {
       const int l = lv + k;
-      fa.im[0][k] = c->im[0][l]; fa.im[1][k] = c->im[1][l]; fa.dx[k] = c->dx0[l]; fa.dy[k] = c->dy0[l];
+      fa.im[0][k] = d0.im[l]; fa.im[1][k] = d1.im[l]; fa.dx[k] = d0.dx[l]; fa.dy[k] = d0.dy[l];
       fa.stride[k] = c->lev_stride[l]; fa.w[k] = c->geom[l].w; fa.h[k] = c->geom[l].h;
     }
     fa.nlev = nlev; fa.first_used = c->p.sc_l - lv; fa.ps = ps;
@@ -493,8 +503,8 @@ static int pyramid_impl(fotg_ctx *c, int n, const T *I0, const T *I1, hipStream_
     for (int l = lv + 1; l <= c->p.sc_f; ++l) {
       const LevelGeom &gs = c->geom[l - 1], &gd = c->geom[l];
       const int tot = gd.w * gd.h * NOC;
-      pyr_halve_kernel<NOC><<<dim3((tot + 255) / 256, 2 * n), 256, 0, s>>>(c->im[0][l - 1], c->lev_stride[l - 1], gs.tw, c->im[0][l], c->lev_stride[l], gd.tw,
-                                                                           gd.w, gd.h, ps, c->im[1][l - 1], c->im[1][l], n);
+      pyr_halve_kernel<NOC><<<dim3((tot + 255) / 256, 2 * n), 256, 0, s>>>(d0.im[l - 1], c->lev_stride[l - 1], gs.tw, d0.im[l], c->lev_stride[l], gd.tw,
+                                                                           gd.w, gd.h, ps, d1.im[l - 1], d1.im[l], n);
       LAUNCHCHK();
     }
     PyrBorderArgs ba;
@@ -502,7 +512,7 @@ static int pyramid_impl(fotg_ctx *c, int n, const T *I0, const T *I1, hipStream_
     int nl = 0, maxtot = 0;
     for (int l = c->p.sc_l; l <= c->p.sc_f; ++l, ++nl) {
       const LevelGeom &g = c->geom[l];
-      ba.im[0][nl] = c->im[0][l]; ba.im[1][nl] = c->im[1][l]; ba.dx[nl] = c->dx0[l]; ba.dy[nl] = c->dy0[l];
+      ba.im[0][nl] = d0.im[l]; ba.im[1][nl] = d1.im[l]; ba.dx[nl] = d0.dx[l]; ba.dy[nl] = d0.dy[l];
       ba.stride[nl] = c->lev_stride[l]; ba.w[nl] = g.w; ba.h[nl] = g.h;
       const int tot = g.tw * g.th * NOC;
       maxtot = tot > maxtot ? tot : maxtot;
@@ -514,18 +524,19 @@ static int pyramid_impl(fotg_ctx *c, int n, const T *I0, const T *I1, hipStream_
   }
   for (int which = 0; which < 2; ++which) {
     if (!(which == 0 ? I0 : I1)) continue;
+    const PyrBufs &d = which == 0 ? d0 : d1;
     for (int l = lv + 1; l <= c->p.sc_f; ++l) {
       const LevelGeom &gs = c->geom[l - 1], &gd = c->geom[l];
       const int tot = gd.w * gd.h * NOC;
-      pyr_halve_kernel<NOC><<<dim3((tot + 255) / 256, n), 256, 0, s>>>(c->im[which][l - 1], c->lev_stride[l - 1], gs.tw,
-                                                                       c->im[which][l], c->lev_stride[l], gd.tw, gd.w, gd.h, ps);
+      pyr_halve_kernel<NOC><<<dim3((tot + 255) / 256, n), 256, 0, s>>>(d.im[l - 1], c->lev_stride[l - 1], gs.tw,
+                                                                       d.im[l], c->lev_stride[l], gd.tw, gd.w, gd.h, ps);
       LAUNCHCHK();
     }
     for (int l = c->p.sc_l; l <= c->p.sc_f; ++l) {
       const LevelGeom &g = c->geom[l];
       const int tot = g.tw * g.th * NOC;
       pyr_border_grad_kernel<NOC><<<dim3((tot + 255) / 256, n), 256, 0, s>>>(
-          c->im[which][l], which == 0 ? c->dx0[l] : nullptr, which == 0 ? c->dy0[l] : nullptr, c->lev_stride[l], g.w, g.h, ps);
+          d.im[l], which == 0 ? d.dx[l] : nullptr, which == 0 ? d.dy[l] : nullptr, c->lev_stride[l], g.w, g.h, ps);
       LAUNCHCHK();
     }
   }
@@ -534,10 +545,10 @@ static int pyramid_impl(fotg_ctx *c, int n, const T *I0, const T *I1, hipStream_
 
 // the pyramid of a flow call: channels of the context; 8-bit colour frames of a gray context (u8_color) are converted on load
 template <typename T>
-static int pyramid_any(fotg_ctx *c, int n, const T *I0, const T *I1, hipStream_t s)
+static int pyramid_any(fotg_ctx *c, int n, const T *I0, const T *I1, const PyrBufs &d0, const PyrBufs &d1, hipStream_t s, int stages = 3)
 {
-  if constexpr (sizeof(T) == 1) { if (c->p.u8_color) return pyramid_impl<1, T, 3>(c, n, I0, I1, s); }
-  return c->noc == 1 ? pyramid_impl<1, T>(c, n, I0, I1, s) : pyramid_impl<3, T>(c, n, I0, I1, s);
+  if constexpr (sizeof(T) == 1) { if (c->p.u8_color) return pyramid_impl<1, T, 3>(c, n, I0, I1, d0, d1, s, stages); }
+  return c->noc == 1 ? pyramid_impl<1, T>(c, n, I0, I1, d0, d1, s, stages) : pyramid_impl<3, T>(c, n, I0, I1, d0, d1, s, stages);
 }
 
 extern "C" {
@@ -547,7 +558,7 @@ int fotg_pyramid(fotg_ctx *c, int n, const float *I, int which, void *stream)
   if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
   ON_DEVICE(c->device);
   const float *I0 = which == 0 ? I : nullptr, *I1 = which == 1 ? I : nullptr;
-  return c->noc == 1 ? pyramid_impl<1>(c, n, I0, I1, (hipStream_t)stream) : pyramid_impl<3>(c, n, I0, I1, (hipStream_t)stream);
+  return pyramid_any<float>(c, n, I0, I1, c->pyr[0], c->pyr[1], (hipStream_t)stream);
 }
 
 int fotg_pyramid_pair(fotg_ctx *c, int n, const float *I0, const float *I1, int stages, void *stream)
@@ -555,7 +566,7 @@ int fotg_pyramid_pair(fotg_ctx *c, int n, const float *I0, const float *I1, int 
   if (!c || !I0 || !I1 || !(stages & 3)) return FOTG_ERR_ARG;
   if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
   ON_DEVICE(c->device);
-  return c->noc == 1 ? pyramid_impl<1>(c, n, I0, I1, (hipStream_t)stream, stages) : pyramid_impl<3>(c, n, I0, I1, (hipStream_t)stream, stages);
+  return pyramid_any<float>(c, n, I0, I1, c->pyr[0], c->pyr[1], (hipStream_t)stream, stages);
 }
 
 int fotg_pyramid_pair_u8(fotg_ctx *c, int n, const unsigned char *I0, const unsigned char *I1, int stages, void *stream)
@@ -563,17 +574,16 @@ int fotg_pyramid_pair_u8(fotg_ctx *c, int n, const unsigned char *I0, const unsi
   if (!c || !I0 || !I1 || !(stages & 3)) return FOTG_ERR_ARG;
   if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
   ON_DEVICE(c->device);
-  if (c->p.u8_color) return pyramid_impl<1, unsigned char, 3>(c, n, I0, I1, (hipStream_t)stream, stages);
-  return c->noc == 1 ? pyramid_impl<1, unsigned char>(c, n, I0, I1, (hipStream_t)stream, stages) : pyramid_impl<3, unsigned char>(c, n, I0, I1, (hipStream_t)stream, stages);
+  return pyramid_any<unsigned char>(c, n, I0, I1, c->pyr[0], c->pyr[1], (hipStream_t)stream, stages);
 }
 
 int fotg_level_ptr(fotg_ctx *c, int which, int l, int kind, float **ptr, long *pair_stride)
 {
   if (!c || !ptr || l < c->p.sc_l || l > c->p.sc_f || (which != 0 && which != 1)) return FOTG_ERR_ARG;
   float *p = nullptr;
-  if (kind == 0) p = c->im[which][l];
-  else if (which == 0 && kind == 1) p = c->dx0[l];
-  else if (which == 0 && kind == 2) p = c->dy0[l];
+  if (kind == 0) p = c->pyr[which].im[l];
+  else if (which == 0 && kind == 1) p = c->pyr[0].dx[l];
+  else if (which == 0 && kind == 2) p = c->pyr[0].dy[l];
   if (!p) return FOTG_ERR_ARG;
   *ptr = p;
   if (pair_stride) *pair_stride = c->lev_stride[l];
@@ -595,7 +605,7 @@ int fotg_grid_init(fotg_ctx *c, int l, int n, const float *I0, const float *I0x,
   (void)stream;
   int st = check_level(c, l, n); if (st) return st;
   if (!I0 || !I0x || !I0y) return FOTG_ERR_ARG;
-  GridState &g = c->gs[l];
+  GridState &g = c->fw.gs[l];
   g.I0 = I0; g.I0x = I0x; g.I0y = I0y; g.stride = pair_stride;
   g.flow_prev = nullptr;                                            // p_init.setZero() (patchgrid.cpp:113)
   return FOTG_OK;
@@ -604,9 +614,10 @@ int fotg_grid_set_target(fotg_ctx *c, int l, const float *I1, long pair_stride)
 {
   int st = check_level(c, l, 1); if (st) return st;
   if (!I1) return FOTG_ERR_ARG;
-  c->gs[l].I1 = I1;
-  if (c->gs[l].stride && c->gs[l].stride != pair_stride) return FOTG_ERR_ARG;
-  c->gs[l].stride = pair_stride;
+  GridState &g = c->fw.gs[l];
+  g.I1 = I1;
+  if (g.stride && g.stride != pair_stride) return FOTG_ERR_ARG;
+  g.stride = pair_stride;
   return FOTG_OK;
 }
 int fotg_grid_init_from_coarser(fotg_ctx *c, int l, int n, const float *flow_prev, void *stream)
@@ -614,24 +625,43 @@ int fotg_grid_init_from_coarser(fotg_ctx *c, int l, int n, const float *flow_pre
   (void)stream;
   int st = check_level(c, l, n); if (st) return st;
   if (!flow_prev) return FOTG_ERR_ARG;
-  c->gs[l].flow_prev = flow_prev;
+  c->fw.gs[l].flow_prev = flow_prev;
   return FOTG_OK;
 }
 int fotg_grid_set_trace(fotg_ctx *c, int l, float *trace_host)
 {
   int st = check_level(c, l, 1); if (st) return st;
   if (trace_host) { st = fotg_enable_taps(c, 1); if (st) return st; }
-  c->gs[l].trace_host = trace_host;
+  c->fw.gs[l].trace_host = trace_host;
   return FOTG_OK;
 }
+}  // extern "C"
 
-int fotg_grid_optimize(fotg_ctx *c, int l, int n, void *stream)
+// The context's (patch size, channels) as compile-time constants: f(integral_constant<int, PS>, integral_constant<int, NOC>) for the
+// pairs fotg_create accepts -- the one place the kernels' <PS, NOC> instantiations are chosen.
+template <typename F>
+static int with_ps_noc(const fotg_ctx *c, F &&f)
 {
-  int st = check_level(c, l, n); if (st) return st;
-  ON_DEVICE(c->device);
-  GridState &gs = c->gs[l];
+  using std::integral_constant;
+  switch (c->ps * 10 + c->noc) {
+    case 41:  f(integral_constant<int, 4>{}, integral_constant<int, 1>{}); return FOTG_OK;
+    case 43:  f(integral_constant<int, 4>{}, integral_constant<int, 3>{}); return FOTG_OK;
+    case 81:  f(integral_constant<int, 8>{}, integral_constant<int, 1>{}); return FOTG_OK;
+    case 83:  f(integral_constant<int, 8>{}, integral_constant<int, 3>{}); return FOTG_OK;
+    case 121: f(integral_constant<int, 12>{}, integral_constant<int, 1>{}); return FOTG_OK;
+    case 123: f(integral_constant<int, 12>{}, integral_constant<int, 3>{}); return FOTG_OK;
+    case 161: f(integral_constant<int, 16>{}, integral_constant<int, 1>{}); return FOTG_OK;
+    case 163: f(integral_constant<int, 16>{}, integral_constant<int, 3>{}); return FOTG_OK;
+  }
+  return FOTG_ERR_ARG;
+}
+
+// Optimize of grid gr at level l.  The tap buffers belong to the forward grid; the per-iteration trace to whichever grid has one set
+// (only the forward one can: fotg_grid_set_trace).
+static int grid_optimize(fotg_ctx *c, Grid &gr, int l, int n, hipStream_t s)
+{
+  GridState &gs = gr.gs[l];
   if (!gs.I0 || !gs.I1) return FOTG_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
   const LevelGeom &g = c->geom[l];
   LkArgs a;
   memset(&a, 0, sizeof(a));
@@ -639,8 +669,8 @@ int fotg_grid_optimize(fotg_ctx *c, int l, int n, void *stream)
   a.flow_prev = gs.flow_prev;
   a.flow_prev_stride = (long)(g.w / 2) * (g.h / 2) * c->nch;
   a.camlr = gs.camlr;
-  a.p_iter = c->p_iter[l]; a.pweight = c->pweight[l];
-  if (c->taps) { a.tmpl = c->tap_t[l]; a.tdx = c->tap_tx[l]; a.tdy = c->tap_ty[l]; a.hes = c->tap_hes[l]; a.cnt = c->tap_cnt[l]; }
+  a.p_iter = gr.p_iter[l]; a.pweight = gr.pweight[l];
+  if (c->taps && &gr == &c->fw) { a.tmpl = c->tap_t[l]; a.tdx = c->tap_tx[l]; a.tdy = c->tap_ty[l]; a.hes = c->tap_hes[l]; a.cnt = c->tap_cnt[l]; }
   a.trace = gs.trace_host ? c->trace_dev[l] : nullptr;
   a.g = g;
   a.max_iter = c->p.max_iter; a.min_iter = c->p.min_iter; a.patnorm = c->p.patnorm;
@@ -682,41 +712,22 @@ int fotg_grid_optimize(fotg_ctx *c, int l, int n, void *stream)
     dim3 gridf((g.nop + 3) / 4, n);
     a.nwg = 0;
     if (banded && gridf.x >= 64) { a.nwg = (int)gridf.x; gridf.x = (gridf.x + 7) & ~7u; }
-#define LKF(PS_, NOC_, R_) lk_fast_kernel<PS_, NOC_, 16, R_><<<gridf, block, 0, s>>>(a)
-    switch (c->ps * 10 + c->noc) {
-      case 41: LKF(4, 1, 0); break;   case 43: LKF(4, 3, 0); break;
-      case 81: if (small) LKF(8, 1, 2); else LKF(8, 1, 0); break;
-      case 83: LKF(8, 3, 0); break;
-      case 121: if (small) LKF(12, 1, 2); else LKF(12, 1, 0); break;
-      case 123: LKF(12, 3, 0); break;
-      case 161: LKF(16, 1, 0); break; default: LKF(16, 3, 0); break;
-    }
-#undef LKF
+    const int st = with_ps_noc(c, [&](auto PS, auto NOC) {
+      if constexpr (NOC == 1 && (PS == 8 || PS == 12)) { if (small) { lk_fast_kernel<PS, NOC, 16, 2><<<gridf, block, 0, s>>>(a); return; } }
+      lk_fast_kernel<PS, NOC, 16, 0><<<gridf, block, 0, s>>>(a);
+    });
+    if (st) return st;
     LAUNCHCHK();
     return FOTG_OK;
   }
-#define LK(PS_, NOC_) do { if (lpp8 && (PS_ == 8 || PS_ == 12) && NOC_ == 1) lk_kernel<(PS_ == 8 || PS_ == 12) ? PS_ : 8, 1, false, true, true, 8><<<grid, block, 0, s>>>(a); \
-                           else if (a.costfct == 0 && shw) lk_kernel<PS_, NOC_, false, true, true><<<grid, block, 0, s>>>(a); \
-                           else if (a.costfct == 0) lk_kernel<PS_, NOC_, false, true><<<grid, block, 0, s>>>(a); \
-                           else lk_kernel<PS_, NOC_, false><<<grid, block, 0, s>>>(a); } while (0)
-#define LKD(PS_, NOC_) lk_kernel<PS_, NOC_, true><<<grid, block, 0, s>>>(a)
-  if (c->p.depth) {
-    switch (c->ps * 10 + c->noc) {
-      case 41: LKD(4, 1); break;   case 43: LKD(4, 3); break;
-      case 81: LKD(8, 1); break;   case 83: LKD(8, 3); break;
-      case 121: LKD(12, 1); break; case 123: LKD(12, 3); break;
-      case 161: LKD(16, 1); break; default: LKD(16, 3); break;
-    }
-  } else {
-    switch (c->ps * 10 + c->noc) {
-      case 41: LK(4, 1); break;   case 43: LK(4, 3); break;
-      case 81: LK(8, 1); break;   case 83: LK(8, 3); break;
-      case 121: LK(12, 1); break; case 123: LK(12, 3); break;
-      case 161: LK(16, 1); break; default: LK(16, 3); break;
-    }
-  }
-#undef LK
-#undef LKD
+  const int st = with_ps_noc(c, [&](auto PS, auto NOC) {
+    if (c->p.depth) { lk_kernel<PS, NOC, true><<<grid, block, 0, s>>>(a); return; }
+    if constexpr (NOC == 1 && (PS == 8 || PS == 12)) { if (lpp8) { lk_kernel<PS, 1, false, true, true, 8><<<grid, block, 0, s>>>(a); return; } }
+    if (a.costfct == 0 && shw) lk_kernel<PS, NOC, false, true, true><<<grid, block, 0, s>>>(a);
+    else if (a.costfct == 0) lk_kernel<PS, NOC, false, true><<<grid, block, 0, s>>>(a);
+    else lk_kernel<PS, NOC, false><<<grid, block, 0, s>>>(a);
+  });
+  if (st) return st;
   LAUNCHCHK();
   if (gs.trace_host) {
     HIPCHK(hipStreamSynchronize(s));
@@ -725,40 +736,37 @@ int fotg_grid_optimize(fotg_ctx *c, int l, int n, void *stream)
   return FOTG_OK;
 }
 
-// AggregateFlowDense of the grid (p_iter, pweight); cg_*: the complementary grid set by SetComplGrid or nullptr
-static int aggregate_impl(fotg_ctx *c, int l, int n, const float *p_iter, const float *pweight, const float *cg_p_iter,
-                          const float *cg_pweight, float *flowout, hipStream_t s)
+// AggregateFlowDense of grid gr; cg: the complementary grid set by SetComplGrid or nullptr
+static int aggregate_impl(fotg_ctx *c, const Grid &gr, const Grid *cg, int l, int n, float *flowout, hipStream_t s)
 {
   const LevelGeom &g = c->geom[l];
   const long fs = (long)g.w * g.h * c->nch;
   const int nch = c->nch;
-  if (cg_p_iter) {
+  const float *p_iter = gr.p_iter[l], *pweight = gr.pweight[l];
+  int st;
+  if (cg) {
     dim3 grid(((g.w + 15) / 16) * ((g.h + 15) / 16), n), block(256);
-#define DFB(PS_, NOC_) densify_fb_kernel<PS_, NOC_><<<grid, block, 0, s>>>(p_iter, pweight, cg_p_iter, cg_pweight, flowout, fs, g, nch)
-    if (c->ps == 4) { if (c->noc == 1) DFB(4, 1); else DFB(4, 3); }
-    else if (c->ps == 16) { if (c->noc == 1) DFB(16, 1); else DFB(16, 3); }
-#undef DFB
-    else if (c->ps == 8 && c->noc == 1) densify_fb_kernel<8, 1><<<grid, block, 0, s>>>(p_iter, pweight, cg_p_iter, cg_pweight, flowout, fs, g, nch);
-    else if (c->ps == 8) densify_fb_kernel<8, 3><<<grid, block, 0, s>>>(p_iter, pweight, cg_p_iter, cg_pweight, flowout, fs, g, nch);
-    else if (c->noc == 1) densify_fb_kernel<12, 1><<<grid, block, 0, s>>>(p_iter, pweight, cg_p_iter, cg_pweight, flowout, fs, g, nch);
-    else densify_fb_kernel<12, 3><<<grid, block, 0, s>>>(p_iter, pweight, cg_p_iter, cg_pweight, flowout, fs, g, nch);
-    LAUNCHCHK();
-    return FOTG_OK;
+    st = with_ps_noc(c, [&](auto PS, auto NOC) {
+      densify_fb_kernel<PS, NOC><<<grid, block, 0, s>>>(p_iter, pweight, cg->p_iter[l], cg->pweight[l], flowout, fs, g, nch);
+    });
+  } else {
+    dim3 grid((g.w * g.h + 255) / 256, n), block(256);
+    // (n not a multiple of 8: XCD-banded placement, see xcd_banded_x; only worth it for launches that span the chip)
+    int nwg = 0;
+    if ((n & 7) != 0 && grid.x >= 64) { nwg = (int)grid.x; grid.x = (grid.x + 7) & ~7u; }
+    st = with_ps_noc(c, [&](auto PS, auto NOC) { densify_kernel<PS, NOC><<<grid, block, 0, s>>>(p_iter, pweight, flowout, fs, g, nch, nwg); });
   }
-  dim3 grid((g.w * g.h + 255) / 256, n), block(256);
-  // (n not a multiple of 8: XCD-banded placement, see xcd_banded_x; only worth it for launches that span the chip)
-  int nwg = 0;
-  if ((n & 7) != 0 && grid.x >= 64) { nwg = (int)grid.x; grid.x = (grid.x + 7) & ~7u; }
-#define DF(PS_, NOC_) densify_kernel<PS_, NOC_><<<grid, block, 0, s>>>(p_iter, pweight, flowout, fs, g, nch, nwg)
-  if (c->ps == 4) { if (c->noc == 1) DF(4, 1); else DF(4, 3); }
-  else if (c->ps == 16) { if (c->noc == 1) DF(16, 1); else DF(16, 3); }
-#undef DF
-  else if (c->ps == 8 && c->noc == 1) densify_kernel<8, 1><<<grid, block, 0, s>>>(p_iter, pweight, flowout, fs, g, nch, nwg);
-  else if (c->ps == 8) densify_kernel<8, 3><<<grid, block, 0, s>>>(p_iter, pweight, flowout, fs, g, nch, nwg);
-  else if (c->noc == 1) densify_kernel<12, 1><<<grid, block, 0, s>>>(p_iter, pweight, flowout, fs, g, nch, nwg);
-  else densify_kernel<12, 3><<<grid, block, 0, s>>>(p_iter, pweight, flowout, fs, g, nch, nwg);
+  if (st) return st;
   LAUNCHCHK();
   return FOTG_OK;
+}
+
+extern "C" {
+int fotg_grid_optimize(fotg_ctx *c, int l, int n, void *stream)
+{
+  int st = check_level(c, l, n); if (st) return st;
+  ON_DEVICE(c->device);
+  return grid_optimize(c, c->fw, l, n, (hipStream_t)stream);
 }
 
 int fotg_grid_aggregate(fotg_ctx *c, int l, int n, float *flowout, void *stream)
@@ -766,7 +774,7 @@ int fotg_grid_aggregate(fotg_ctx *c, int l, int n, float *flowout, void *stream)
   int st = check_level(c, l, n); if (st) return st;
   if (!flowout) return FOTG_ERR_ARG;
   ON_DEVICE(c->device);
-  return aggregate_impl(c, l, n, c->p_iter[l], c->pweight[l], nullptr, nullptr, flowout, (hipStream_t)stream);
+  return aggregate_impl(c, c->fw, nullptr, l, n, flowout, (hipStream_t)stream);
 }
 
 int fotg_grid_read(fotg_ctx *c, int l, int pair, float *p_iter, float *pweight, float *tmpl, float *tdx, float *tdy,
@@ -777,8 +785,8 @@ int fotg_grid_read(fotg_ctx *c, int l, int pair, float *p_iter, float *pweight, 
   ON_DEVICE(c->device);
   HIPCHK(hipDeviceSynchronize());
   const size_t nop = c->geom[l].nop, nv = (size_t)c->ps * c->ps * c->noc, pb = (size_t)pair * nop;
-  if (p_iter) HIPCHK(hipMemcpy(p_iter, c->p_iter[l] + pb * 2, nop * 2 * 4, hipMemcpyDeviceToHost));
-  if (pweight) HIPCHK(hipMemcpy(pweight, c->pweight[l] + pb * nv, nop * nv * 4, hipMemcpyDeviceToHost));
+  if (p_iter) HIPCHK(hipMemcpy(p_iter, c->fw.p_iter[l] + pb * 2, nop * 2 * 4, hipMemcpyDeviceToHost));
+  if (pweight) HIPCHK(hipMemcpy(pweight, c->fw.pweight[l] + pb * nv, nop * nv * 4, hipMemcpyDeviceToHost));
   if (tmpl || tdx || tdy || hes || cnt) {
     if (!c->taps) return FOTG_ERR_ARG;
     if (tmpl) HIPCHK(hipMemcpy(tmpl, c->tap_t[l] + pb * nv, nop * nv * 4, hipMemcpyDeviceToHost));
@@ -1260,14 +1268,14 @@ int fotg_bench_sor_call(fotg_ctx *c, int l, int n, void *stream)
 int fotg_varref(fotg_ctx *c, int l, int n, const float *I0, const float *I1, long pair_stride, float *flow, void *stream)
 {
   if (!c || l < 0 || l >= FOTG_MAXLEV) return FOTG_ERR_ARG;
-  return varref_dispatch(c, l, n, I0, I1, pair_stride, flow, (hipStream_t)stream, c->gs[l].camlr);
+  return varref_dispatch(c, l, n, I0, I1, pair_stride, flow, (hipStream_t)stream, c->fw.gs[l].camlr);
 }
 
 int fotg_grid_set_camera(fotg_ctx *c, int l, int camlr)
 {
   int st = check_level(c, l, 1); if (st) return st;
   if (camlr != 0 && camlr != 1) return FOTG_ERR_ARG;
-  c->gs[l].camlr = camlr;
+  c->fw.gs[l].camlr = camlr;
   return FOTG_OK;
 }
 
@@ -1332,12 +1340,41 @@ int fotg_varref_plane(fotg_ctx *c, int pair, const char *name, int l, float *hos
 /* ------------------------------------------------------------------------------------------------ */
 /* whole flow: OFClass::calc (src/oflow.cpp:211-368) with kroeger numerics (kroeger/oflow.cpp:184-337)   */
 /* ------------------------------------------------------------------------------------------------ */
-// the scale loop for pairs [0, n) of context (view) c on one stream
 }  // extern "C"
+
+// One flow direction at one level (kroeger/oflow.cpp:190-295): its grid, the template frame with its gradients, the target frame,
+// the flow LK starts from (the direction's coarser flow, an init flow or nullptr) and where the level's flow goes (nullptr: the
+// direction only serves the other one's merge at this level).  cg: the complementary grid the densification merges (usefbcon).
+// camlr: camera side of the refinement (depth mode); the grid carries its own.
+struct LevelDir {
+  Grid *grid;
+  const Grid *cg;
+  const float *tmpl, *tx, *ty, *tgt, *init;
+  float *out;
+  int camlr;
+};
+enum { LV_LK = 1, LV_DENSIFY = 2, LV_REFINE = 4, LV_ALL = 7 };
+
+// the stages of `stages`, in order: grid init + target + initialisation + LK, densification, refinement
+static int run_level(fotg_ctx *c, int l, int n, const LevelDir &d, int stages, hipStream_t s)
+{
+  int st;
+  if (stages & LV_LK) {
+    GridState &g = d.grid->gs[l];
+    g.I0 = d.tmpl; g.I0x = d.tx; g.I0y = d.ty; g.I1 = d.tgt; g.stride = c->lev_stride[l];
+    g.flow_prev = d.init;
+    if ((st = grid_optimize(c, *d.grid, l, n, s))) return st;
+  }
+  if ((stages & LV_DENSIFY) && d.out && (st = aggregate_impl(c, *d.grid, d.cg, l, n, d.out, s))) return st;
+  if ((stages & LV_REFINE) && d.out && c->p.usetvref && (st = varref_dispatch(c, l, n, d.tmpl, d.tgt, c->lev_stride[l], d.out, s, d.camlr))) return st;
+  return FOTG_OK;
+}
+
+// the scale loop for pairs [0, n) of context c on one stream
 // I1 == nullptr: sequence mode -- I0 holds n+1 consecutive frames, pair k is (frame k, frame k+1); every frame's pyramid
 // is built once (with gradients) and serves as the target of pair k-1 and the template source of pair k.
 // outflow_bw != nullptr: bidirectional (fotg_calc_bidir, contexts created with fotg_params::bidir) -- the backward flow of every
-// pair (template = its frame 1, target = its frame 0, initialised from initflow_bw) runs on the backward grid view at every level,
+// pair (template = its frame 1, target = its frame 0, initialised from initflow_bw) runs on the backward grid at every level,
 // the finest one included, with the same steps as the forward one; each frame's pyramid is built once, with gradients.
 template <typename T>
 static int calc_range(fotg_ctx *c, int n, const T *I0, const T *I1, const float *initflow, float *outflow, hipStream_t stream,
@@ -1358,97 +1395,34 @@ static int calc_range(fotg_ctx *c, int n, const T *I0, const T *I1, const float 
     (void)hipEventRecord(c->tev[nev++], stream);
   };
   mark();
-  // the backward grid lives in a view of the context whose grid arrays are the *_bw ones (nothing is owned by the view)
-  fotg_ctx *vb = nullptr;
-  struct ViewGuard { fotg_ctx *&v; ~ViewGuard() { free(v); } } guard{vb};
-  if (fb || bidir) {
-    vb = (fotg_ctx *)malloc(sizeof(fotg_ctx));
-    if (!vb) return FOTG_ERR_ARG;
-    memcpy((void *)vb, (const void *)c, sizeof(fotg_ctx));
-    vb->taps = false;
-    for (int l = c->p.sc_l; l <= c->p.sc_f; ++l) {
-      vb->p_iter[l] = c->p_iter_bw[l]; vb->pweight[l] = c->pweight_bw[l];
-      memset((void *)&vb->gs[l], 0, sizeof(GridState));
-      // kroeger/oflow.cpp:157,165: the backward grid of the merge is the right camera; a plain bidirectional call's backward
-      // grid is what a one-direction call on the swapped pair runs (camlr only clamps in depth mode, which bidir refuses)
-      vb->gs[l].camlr = fb ? 1 : c->gs[l].camlr;
-    }
-  }
+  const PyrBufs &f0 = c->pyr[0], &f1 = c->pyr[1];
   if ((fb || bidir) && !seq) {
     // both frames need gradients: two template-type pyramids (the second one into the frame-1 buffers)
-    if ((st = pyramid_any<T>(c, n, I0, (const T *)nullptr, stream))) return st;
-    fotg_ctx *v1 = (fotg_ctx *)malloc(sizeof(fotg_ctx));
-    if (!v1) return FOTG_ERR_ARG;
-    memcpy((void *)v1, (const void *)c, sizeof(fotg_ctx));
-    for (int l = c->base_lv; l <= c->p.sc_f; ++l) { v1->im[0][l] = c->im[1][l]; v1->dx0[l] = c->dx1[l]; v1->dy0[l] = c->dy1[l]; }
-    st = pyramid_any<T>(v1, n, I1, (const T *)nullptr, stream);
-    free(v1);
-    if (st) return st;
-  } else if ((st = pyramid_any<T>(c, nimg, I0, I1, stream))) return st;
+    if ((st = pyramid_any<T>(c, n, I0, (const T *)nullptr, f0, f1, stream))) return st;
+    if ((st = pyramid_any<T>(c, n, I1, (const T *)nullptr, f1, f1, stream))) return st;
+  } else if ((st = pyramid_any<T>(c, nimg, I0, I1, f0, f1, stream))) return st;
   mark();
   for (int l = c->p.sc_f; l >= c->p.sc_l; --l) {
     const long ls = c->lev_stride[l];
-    const float *tgt = seq ? c->im[0][l] + ls : c->im[1][l];
-    if (fb) {
-      // kroeger/oflow.cpp:190-235 and :262-295 with usefbcon: both grids, each one's densification merges the other's patches
-      const float *tx = seq ? c->dx0[l] + ls : c->dx1[l], *ty = seq ? c->dy0[l] + ls : c->dy1[l];
-      if ((st = fotg_grid_init(c, l, n, c->im[0][l], c->dx0[l], c->dy0[l], ls, stream))) return st;
-      if ((st = fotg_grid_set_target(c, l, tgt, ls))) return st;
-      if ((st = fotg_grid_init(vb, l, n, tgt, tx, ty, ls, stream))) return st;
-      if ((st = fotg_grid_set_target(vb, l, c->im[0][l], ls))) return st;
-      if (l < c->p.sc_f) {
-        if ((st = fotg_grid_init_from_coarser(c, l, n, c->flow[l + 1], stream))) return st;
-        if ((st = fotg_grid_init_from_coarser(vb, l, n, c->flow_bw[l + 1], stream))) return st;
-      } else if (initflow) { if ((st = fotg_grid_init_from_coarser(c, l, n, initflow, stream))) return st; }
-      if ((st = fotg_grid_optimize(c, l, n, stream))) return st;
-      if ((st = fotg_grid_optimize(vb, l, n, stream))) return st;
+    const bool top = l == c->p.sc_f, last = l == c->p.sc_l;
+    // frame 1 of pair k: the next frame of the sequence pyramid, or the frame-1 buffers (gradients: usefbcon / bidir only)
+    const float *tgt = seq ? f0.im[l] + ls : f1.im[l], *tx = seq ? f0.dx[l] + ls : f1.dx[l], *ty = seq ? f0.dy[l] + ls : f1.dy[l];
+    const LevelDir fwd = {&c->fw, fb ? &c->bw : nullptr, f0.im[l], f0.dx[l], f0.dy[l], tgt, top ? initflow : c->flow[l + 1],
+                          last ? outflow : c->flow[l], 0};
+    // kroeger/oflow.cpp:157,165: the backward grid of the merge is the right camera, and only its forward grid takes an init flow;
+    // a plain bidirectional call's backward grid is what a one-direction call on the swapped pair runs (camlr only clamps in depth
+    // mode, which bidir refuses).  bidir: the backward flow of the finest level too, into outflow_bw.
+    const LevelDir bwd = {&c->bw, fb ? &c->fw : nullptr, tgt, tx, ty, f0.im[l], top ? (fb ? nullptr : initflow_bw) : c->flow_bw[l + 1],
+                          last ? outflow_bw : c->flow_bw[l], fb ? 1 : 0};
+    if (fb || bidir) c->bw.gs[l].camlr = fb ? 1 : c->fw.gs[l].camlr;
+    // usefbcon: both grids stage by stage (each one's densification merges the other's patches); bidir without it: two independent
+    // directions on one workspace, the forward one completely, then the backward one
+    for (int stage = LV_LK; stage <= LV_REFINE; stage <<= 1) {
+      if ((st = run_level(c, l, n, fwd, stage, stream))) return st;
+      if (fb && (st = run_level(c, l, n, bwd, stage, stream))) return st;
       mark();
-      float *out = (l == c->p.sc_l) ? outflow : c->flow[l];
-      // (bidir: the backward flow of the finest level too, into outflow_bw)
-      float *out_bw = (l == c->p.sc_l) ? outflow_bw : c->flow_bw[l];
-      if ((st = aggregate_impl(c, l, n, c->p_iter[l], c->pweight[l], c->p_iter_bw[l], c->pweight_bw[l], out, stream))) return st;
-      if (out_bw && (st = aggregate_impl(c, l, n, c->p_iter_bw[l], c->pweight_bw[l], c->p_iter[l], c->pweight[l], out_bw, stream))) return st;
-      mark();
-      if (c->p.usetvref) {
-        if ((st = varref_dispatch(c, l, n, c->im[0][l], tgt, ls, out, stream, 0))) return st;
-        if (out_bw && (st = varref_dispatch(c, l, n, tgt, c->im[0][l], ls, out_bw, stream, 1))) return st;
-      }
-      mark();
-      continue;
     }
-    if (bidir) {
-      // two independent directions on one workspace, one after the other: the forward one exactly as below, then the backward
-      // one on the view -- template = the pair's frame 1 (with the gradients of its template-type pyramid), target = frame 0
-      const float *tx = seq ? c->dx0[l] + ls : c->dx1[l], *ty = seq ? c->dy0[l] + ls : c->dy1[l];
-      float *out = (l == c->p.sc_l) ? outflow : c->flow[l], *out_bw = (l == c->p.sc_l) ? outflow_bw : c->flow_bw[l];
-      if ((st = fotg_grid_init(c, l, n, c->im[0][l], c->dx0[l], c->dy0[l], ls, stream))) return st;
-      if ((st = fotg_grid_set_target(c, l, tgt, ls))) return st;
-      if (l < c->p.sc_f) { if ((st = fotg_grid_init_from_coarser(c, l, n, c->flow[l + 1], stream))) return st; }
-      else if (initflow) { if ((st = fotg_grid_init_from_coarser(c, l, n, initflow, stream))) return st; }
-      if ((st = fotg_grid_optimize(c, l, n, stream))) return st;
-      if ((st = aggregate_impl(c, l, n, c->p_iter[l], c->pweight[l], nullptr, nullptr, out, stream))) return st;
-      if (c->p.usetvref && (st = varref_dispatch(c, l, n, c->im[0][l], tgt, ls, out, stream, 0))) return st;
-      if ((st = fotg_grid_init(vb, l, n, tgt, tx, ty, ls, stream))) return st;
-      if ((st = fotg_grid_set_target(vb, l, c->im[0][l], ls))) return st;
-      if (l < c->p.sc_f) { if ((st = fotg_grid_init_from_coarser(vb, l, n, c->flow_bw[l + 1], stream))) return st; }
-      else if (initflow_bw) { if ((st = fotg_grid_init_from_coarser(vb, l, n, initflow_bw, stream))) return st; }
-      if ((st = fotg_grid_optimize(vb, l, n, stream))) return st;
-      if ((st = aggregate_impl(c, l, n, c->p_iter_bw[l], c->pweight_bw[l], nullptr, nullptr, out_bw, stream))) return st;
-      if (c->p.usetvref && (st = varref_dispatch(c, l, n, tgt, c->im[0][l], ls, out_bw, stream, 0))) return st;
-      continue;
-    }
-    if ((st = fotg_grid_init(c, l, n, c->im[0][l], c->dx0[l], c->dy0[l], c->lev_stride[l], stream))) return st;
-    if ((st = fotg_grid_set_target(c, l, tgt, c->lev_stride[l]))) return st;
-    if (l < c->p.sc_f) { if ((st = fotg_grid_init_from_coarser(c, l, n, c->flow[l + 1], stream))) return st; }
-    else if (initflow) { if ((st = fotg_grid_init_from_coarser(c, l, n, initflow, stream))) return st; }
-    if ((st = fotg_grid_optimize(c, l, n, stream))) return st;
-    mark();
-    float *out = (l == c->p.sc_l) ? outflow : c->flow[l];
-    if ((st = fotg_grid_aggregate(c, l, n, out, stream))) return st;
-    mark();
-    if (c->p.usetvref)
-      if ((st = varref_dispatch(c, l, n, c->im[0][l], tgt, c->lev_stride[l], out, stream, 0))) return st;
-    mark();
+    if (bidir && !fb && (st = run_level(c, l, n, bwd, LV_ALL, stream))) return st;
   }
   if (timing && nev == 2 + 3 * (c->p.sc_f - c->p.sc_l + 1)) {
     // The reference's lines (src/oflow.cpp:343, :356; kroeger/oflow.cpp:303, :358), from the GPU times of the stages.  Patch
@@ -1471,51 +1445,61 @@ static int calc_range(fotg_ctx *c, int n, const T *I0, const T *I1, const float 
   return FOTG_OK;
 }
 
+// The flow entry points for float and 8-bit frames (the pyramid base kernel converts on load, exact, and reads a quarter of the
+// bytes): argument, batch and device preamble, then the scale loop.  seq: I0 holds n + 1 consecutive frames, I1 is not read.
+// bidir: outflow == fotg_calc_batch(I0, I1, initflow), outflow_bw == fotg_calc_batch(I1, I0, initflow_bw), bit for bit, from one
+// pyramid per frame.  FOTG_ERR_ARG: a context created without fotg_params::bidir, a null frame or output pointer, or an initflow
+// with usefbcon (the merge couples the directions; its one-direction form initialises only the forward grid).
+template <typename T>
+static int calc_entry(fotg_ctx *c, int n, const T *I0, const T *I1, bool seq, bool bidir, const float *initflow, const float *initflow_bw,
+                      float *outflow, float *outflow_bw, void *stream)
+{
+  if (!c || !I0 || (!seq && !I1) || !outflow) return FOTG_ERR_ARG;
+  if (bidir && (!c->p.bidir || !outflow_bw || (c->p.usefbcon && (initflow || initflow_bw)))) return FOTG_ERR_ARG;
+  if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
+  ON_DEVICE(c->device);
+  return calc_range<T>(c, n, I0, seq ? nullptr : I1, initflow, outflow, (hipStream_t)stream, initflow_bw, outflow_bw);
+}
+
 extern "C" {
 int fotg_calc_batch(fotg_ctx *c, int n, const float *I0, const float *I1, const float *initflow, float *outflow, void *stream)
 {
-  if (!c || !I0 || !I1 || !outflow) return FOTG_ERR_ARG;
-  if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
-  ON_DEVICE(c->device);
-  return calc_range<float>(c, n, I0, I1, initflow, outflow, (hipStream_t)stream);
+  return calc_entry<float>(c, n, I0, I1, false, false, initflow, nullptr, outflow, nullptr, stream);
 }
-
-/* 8-bit frames (SURVEY 8f "next" row 2): same path, the pyramid base kernel converts on load (exact) and reads a
- * quarter of the bytes.  Eager single-stream launch sequence. */
 int fotg_calc_batch_u8(fotg_ctx *c, int n, const unsigned char *I0, const unsigned char *I1, const float *initflow, float *outflow, void *stream)
 {
-  if (!c || !I0 || !I1 || !outflow) return FOTG_ERR_ARG;
-  if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
-  ON_DEVICE(c->device);
-  return calc_range<unsigned char>(c, n, I0, I1, initflow, outflow, (hipStream_t)stream);
+  return calc_entry<unsigned char>(c, n, I0, I1, false, false, initflow, nullptr, outflow, nullptr, stream);
 }
-
-/* bidirectional flow: outflow == fotg_calc_batch(I0, I1, initflow), outflow_bw == fotg_calc_batch(I1, I0, initflow_bw), bit for bit,
- * from one pyramid per frame.  FOTG_ERR_ARG: a context created without fotg_params::bidir, a null frame or output pointer, or an
- * initflow with usefbcon (the merge couples the directions; its one-direction form initialises only the forward grid). */
-static int bidir_args(fotg_ctx *c, int n, const void *I0, const void *I1, const float *initflow, const float *initflow_bw,
-                      const float *outflow, const float *outflow_bw)
-{
-  if (!c || !c->p.bidir || !I0 || !I1 || !outflow || !outflow_bw) return FOTG_ERR_ARG;
-  if (c->p.usefbcon && (initflow || initflow_bw)) return FOTG_ERR_ARG;
-  if (n < 1 || n > c->max_batch) return FOTG_ERR_BATCH;
-  return FOTG_OK;
-}
-
 int fotg_calc_bidir(fotg_ctx *c, int n, const float *I0, const float *I1, const float *initflow, const float *initflow_bw,
                     float *outflow, float *outflow_bw, void *stream)
 {
-  int st = bidir_args(c, n, I0, I1, initflow, initflow_bw, outflow, outflow_bw); if (st) return st;
-  ON_DEVICE(c->device);
-  return calc_range<float>(c, n, I0, I1, initflow, outflow, (hipStream_t)stream, initflow_bw, outflow_bw);
+  return calc_entry<float>(c, n, I0, I1, false, true, initflow, initflow_bw, outflow, outflow_bw, stream);
 }
-
 int fotg_calc_bidir_u8(fotg_ctx *c, int n, const unsigned char *I0, const unsigned char *I1, const float *initflow,
                        const float *initflow_bw, float *outflow, float *outflow_bw, void *stream)
 {
-  int st = bidir_args(c, n, I0, I1, initflow, initflow_bw, outflow, outflow_bw); if (st) return st;
-  ON_DEVICE(c->device);
-  return calc_range<unsigned char>(c, n, I0, I1, initflow, outflow, (hipStream_t)stream, initflow_bw, outflow_bw);
+  return calc_entry<unsigned char>(c, n, I0, I1, false, true, initflow, initflow_bw, outflow, outflow_bw, stream);
+}
+
+/* sequence mode (SURVEY 8f "next" row 2): n_frames consecutive frames -> n_frames - 1 flows (frame k -> k+1); the bidirectional form:
+ * pair k = (frame k, frame k+1) forward, (frame k+1, frame k) backward; every frame's pyramid once */
+int fotg_calc_sequence(fotg_ctx *c, int n_frames, const float *frames, const float *initflow, float *outflow, void *stream)
+{
+  return calc_entry<float>(c, n_frames - 1, frames, nullptr, true, false, initflow, nullptr, outflow, nullptr, stream);
+}
+int fotg_calc_sequence_u8(fotg_ctx *c, int n_frames, const unsigned char *frames, const float *initflow, float *outflow, void *stream)
+{
+  return calc_entry<unsigned char>(c, n_frames - 1, frames, nullptr, true, false, initflow, nullptr, outflow, nullptr, stream);
+}
+int fotg_calc_sequence_bidir(fotg_ctx *c, int n_frames, const float *frames, const float *initflow, const float *initflow_bw,
+                             float *outflow, float *outflow_bw, void *stream)
+{
+  return calc_entry<float>(c, n_frames - 1, frames, nullptr, true, true, initflow, initflow_bw, outflow, outflow_bw, stream);
+}
+int fotg_calc_sequence_bidir_u8(fotg_ctx *c, int n_frames, const unsigned char *frames, const float *initflow, const float *initflow_bw,
+                                float *outflow, float *outflow_bw, void *stream)
+{
+  return calc_entry<unsigned char>(c, n_frames - 1, frames, nullptr, true, true, initflow, initflow_bw, outflow, outflow_bw, stream);
 }
 
 /* ---- batches in flight ---------------------------------------------------------------------------------------------
@@ -1769,38 +1753,6 @@ int fotg_pipe_context(fotg_pipe *q, int slot, fotg_ctx **ctx)
   if (!q || !ctx || slot < 0 || slot >= q->depth) return FOTG_ERR_ARG;
   *ctx = q->ctx[slot];
   return FOTG_OK;
-}
-
-/* sequence mode (SURVEY 8f "next" row 2): n_frames consecutive frames -> n_frames - 1 flows (frame k -> k+1) */
-int fotg_calc_sequence(fotg_ctx *c, int n_frames, const float *frames, const float *initflow, float *outflow, void *stream)
-{
-  if (!c || !frames || !outflow) return FOTG_ERR_ARG;
-  if (n_frames < 2 || n_frames - 1 > c->max_batch) return FOTG_ERR_BATCH;
-  ON_DEVICE(c->device);
-  return calc_range<float>(c, n_frames - 1, frames, nullptr, initflow, outflow, (hipStream_t)stream);
-}
-int fotg_calc_sequence_u8(fotg_ctx *c, int n_frames, const unsigned char *frames, const float *initflow, float *outflow, void *stream)
-{
-  if (!c || !frames || !outflow) return FOTG_ERR_ARG;
-  if (n_frames < 2 || n_frames - 1 > c->max_batch) return FOTG_ERR_BATCH;
-  ON_DEVICE(c->device);
-  return calc_range<unsigned char>(c, n_frames - 1, frames, nullptr, initflow, outflow, (hipStream_t)stream);
-}
-
-/* the sequence form: pair k = (frame k, frame k+1) forward, (frame k+1, frame k) backward; every frame's pyramid once */
-int fotg_calc_sequence_bidir(fotg_ctx *c, int n_frames, const float *frames, const float *initflow, const float *initflow_bw,
-                             float *outflow, float *outflow_bw, void *stream)
-{
-  int st = bidir_args(c, n_frames - 1, frames, frames, initflow, initflow_bw, outflow, outflow_bw); if (st) return st;
-  ON_DEVICE(c->device);
-  return calc_range<float>(c, n_frames - 1, frames, nullptr, initflow, outflow, (hipStream_t)stream, initflow_bw, outflow_bw);
-}
-int fotg_calc_sequence_bidir_u8(fotg_ctx *c, int n_frames, const unsigned char *frames, const float *initflow, const float *initflow_bw,
-                                float *outflow, float *outflow_bw, void *stream)
-{
-  int st = bidir_args(c, n_frames - 1, frames, frames, initflow, initflow_bw, outflow, outflow_bw); if (st) return st;
-  ON_DEVICE(c->device);
-  return calc_range<unsigned char>(c, n_frames - 1, frames, nullptr, initflow, outflow, (hipStream_t)stream, initflow_bw, outflow_bw);
 }
 
 long fotg_debug_counter(const char *name)
