@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ("warp", "upsample_crop_warp"):
         import importlib
         return getattr(importlib.import_module(".warp", __name__), name)
+    if name in ("chain", "track_points", "upsample_crop_chain", "upsample_crop_track_points"):
+        import importlib
+        return getattr(importlib.import_module(".chain", __name__), name)
     if name in ("interpolate", "upsample_crop_interpolate"):
         from . import interp
         return getattr(interp, name)

@@ -77,6 +77,10 @@ SYMBOLS = [
     ("fotg_interp_u8", C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     ("fotg_upsample_crop_interp", C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     ("fotg_upsample_crop_interp_u8", C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+    ("fotg_flow_chain", C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+    ("fotg_track_points", C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_flow_chain", C.c_int, [vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_track_points", C.c_int, [vp, C.c_int, vp, vp, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp]),
     ("fotg_level_size", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_out_size", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_num_patches", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -24,15 +24,11 @@ namespace fotg {
 
 enum { FB_NCODE = 4 };
 
+// the bilinear sample of flow B (plane `pair`, first pixel `base`) at (X, Y), 0 <= X <= w-1 and 0 <= Y <= h-1: the four clamped
+// taps and the three lerps of the head of this file.  Shared with chain.hip.h, which follows a position through T such samples.
 template <class Src>
-__device__ __forceinline__ unsigned fb_code(const Src &F, const Src &B, int pair, int x, int y, int w, int h, long base,
-                                            float alpha1, float alpha2)
+__device__ __forceinline__ void fb_sample(const Src &B, int pair, long base, float X, float Y, int w, int h, float &bu, float &bv)
 {
-  float u, v;
-  F.at(base + (long)y * w + x, pair, x, y, u, v);
-  if (!__builtin_isfinite(u) || !__builtin_isfinite(v)) return 3;
-  const float X = (float)x + u, Y = (float)y + v;
-  if (!(X >= 0.f && X <= (float)(w - 1) && Y >= 0.f && Y <= (float)(h - 1))) return 2;
   int x0 = (int)floorf(X), y0 = (int)floorf(Y);
   x0 = x0 < w - 1 ? x0 : w - 1;
   y0 = y0 < h - 1 ? y0 : h - 1;
@@ -45,11 +41,30 @@ __device__ __forceinline__ unsigned fb_code(const Src &F, const Src &B, int pair
   B.at(base + (long)y1 * w + x1, pair, x1, y1, u11, v11);
   const float r0u = u00 * (1.f - ax) + u01 * ax, r1u = u10 * (1.f - ax) + u11 * ax;
   const float r0v = v00 * (1.f - ax) + v01 * ax, r1v = v10 * (1.f - ax) + v11 * ax;
-  const float bu = r0u * (1.f - ay) + r1u * ay, bv = r0v * (1.f - ay) + r1v * ay;
+  bu = r0u * (1.f - ay) + r1u * ay; bv = r0v * (1.f - ay) + r1v * ay;
+}
+
+// the inequality: (u, v) and the vector (bu, bv) sampled at its target agree
+__device__ __forceinline__ bool fb_consistent(float u, float v, float bu, float bv, float alpha1, float alpha2)
+{
   const float du = u + bu, dv = v + bv;
   const float lhs = du * du + dv * dv;
   const float rhs = alpha1 * ((u * u + v * v) + (bu * bu + bv * bv)) + alpha2;
-  return lhs < rhs ? 0u : 1u;
+  return lhs < rhs;
+}
+
+template <class Src>
+__device__ __forceinline__ unsigned fb_code(const Src &F, const Src &B, int pair, int x, int y, int w, int h, long base,
+                                            float alpha1, float alpha2)
+{
+  float u, v;
+  F.at(base + (long)y * w + x, pair, x, y, u, v);
+  if (!__builtin_isfinite(u) || !__builtin_isfinite(v)) return 3;
+  const float X = (float)x + u, Y = (float)y + v;
+  if (!(X >= 0.f && X <= (float)(w - 1) && Y >= 0.f && Y <= (float)(h - 1))) return 2;
+  float bu, bv;
+  fb_sample(B, pair, base, X, Y, w, h, bu, bv);
+  return fb_consistent(u, v, bu, bv, alpha1, alpha2) ? 0u : 1u;
 }
 
 // grid (ceil(w h / 1024), n, 2), 256 threads.  counts: n x 2 x 4, zeroed before the launch, or nullptr.  A direction whose mask

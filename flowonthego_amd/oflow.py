@@ -251,6 +251,22 @@ class OFClass:
         from .warp import upsample_crop_warp
         return upsample_crop_warp(self, flow, src, ref=ref, occ=occ, fill=fill, stats=stats, fused=fused)
 
+    def upsample_crop_chain(self, flows, flows_bw=None, alpha1=0.01, alpha2=0.5, stats=False, fused=None):
+        """the T coarse flows of one sequence chained: displacement frame 0 -> T, codes, steps -- flowonthego_amd.chain"""
+        from .chain import upsample_crop_chain
+        return upsample_crop_chain(self, flows, flows_bw, alpha1=alpha1, alpha2=alpha2, stats=stats, fused=fused)
+
+    def upsample_crop_track_points(self, points, flows, flows_bw=None, alpha1=0.01, alpha2=0.5, stats=False, fused=False):
+        """points (P, 2) followed through the T coarse flows of one sequence: trajectories, codes, steps -- flowonthego_amd.chain"""
+        from .chain import upsample_crop_track_points
+        return upsample_crop_track_points(self, points, flows, flows_bw, alpha1=alpha1, alpha2=alpha2, stats=stats, fused=fused)
+
+    def track(self, frames, points=None, alpha1=0.01, alpha2=0.5, stats=False, fused=None):
+        """the flows of frames (T+1, ...) and their chain: every pixel of frame 0 (points=None) or the given points followed to
+        frame T, with an occlusion test per step on a bidir context -- flowonthego_amd.chain"""
+        from .chain import track
+        return track(self, frames, points=points, alpha1=alpha1, alpha2=alpha2, stats=stats, fused=fused)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

@@ -389,6 +389,51 @@ int fotg_upsample_crop_interp_u8(fotg_ctx *ctx, int n, const float *coarse_fw, c
                                  const unsigned char *mask_bw, float alpha1, float alpha2, const unsigned char *ref,
                                  unsigned char *dst, unsigned char *code, double *stats, void *stream);
 
+/* ---- flow chaining: a position followed through the T flows of a sequence, csrc/chain.hip.h ----------------------------------
+ * A chain has a start position (X0, Y0), T forward flows F_0 .. F_{T-1} of one w x h sequence (F_k: frame k -> k+1) and optionally
+ * T backward flows B_k (frame k+1 -> k).  Its state is a displacement (Dx, Dy) = (0, 0), steps = 0 and code = 0.  All arithmetic
+ * f32, every operation rounded on its own, in this order; inside is the in-frame test of the warp (own == 0), bilerp the sample of
+ * the consistency check (x0 = min((int)floorf(X), w-1), x1 = min(x0+1, w-1), ax = X - (float)x0, y alike; per channel
+ * r0 = a*(1-ax) + b*ax, r1 likewise, value = r0*(1-ay) + r1*ay):
+ *   start:  !isfinite(X0) || !isfinite(Y0) -> code 3;  else !inside(X0, Y0) -> code 2
+ *   for k = 0 .. T-1 while code == 0:
+ *     X = X0 + Dx;  Y = Y0 + Dy
+ *     u, v = bilerp(F_k, X, Y)
+ *     if !isfinite(u) || !isfinite(v):            code 3, stop
+ *     Ex = Dx + u;  Ey = Dy + v;  Xn = X0 + Ex;  Yn = Y0 + Ey
+ *     if !inside(Xn, Yn):                         code 2, stop
+ *     with B:  bu, bv = bilerp(B_k, Xn, Yn);  du = u + bu;  dv = v + bv
+ *              lhs = du*du + dv*dv;  rhs = alpha1*((u*u + v*v) + (bu*bu + bv*bv)) + alpha2
+ *              if !(lhs < rhs):                   code 1, stop          (a NaN in B gives 1, as in the consistency check)
+ *     Dx = Ex;  Dy = Ey;  steps = k + 1
+ * A stopped chain keeps its last accepted displacement.  Every tap index comes from a position that has passed inside and is
+ * clamped: no input value (NaN, +-inf, 1e30) produces an out-of-range address.  For T = 1 and integer starts the displacement at
+ * the code-0 pixels is F_0 (==) and, with B, code is the forward mask of the consistency check byte for byte wherever the taps to
+ * the right of, below and diagonally below the pixel are finite (a non-finite tap times the weight 0 is a NaN: code 3).
+ * Dense form: one chain per pixel of frame 0.  flows, flows_bw (or NULL): n_seq x T x h x w x 2 f32 on the device.  Outputs, each
+ * may be NULL (not all four): total n_seq x h x w x 2 f32 (the displacement), code n_seq x h x w uint8, steps n_seq x h x w int32,
+ * stats n_seq x 5 uint64 -- the chains ending with code 0, 1, 2, 3 and the sum of steps, zeroed by the call, integer atomics
+ * (the same bits every run).  One launch walks all T steps; no position is written to memory.  Asynchronous on `stream`.
+ * FOTG_ERR_ARG: n_seq, T, w or h < 1, n_seq > 65535, n_seq T >= 2^31, a null flows, all outputs null, an output overlapping an
+ * input. */
+int fotg_flow_chain(int device, int n_seq, int T, const float *flows, const float *flows_bw, int w, int h, float alpha1, float alpha2,
+                    float *total, unsigned char *code, int *steps, unsigned long long *stats, void *stream);
+/* Point form: pts n_seq x P x 2 f32, (x, y) in pixels, anywhere (outside the frame: code 2 at once, non-finite: code 3).  traj:
+ * n_seq x (T+1) x P x 2 f32, X0 + D after every step, traj[0] the start as given, the frozen position repeated once a chain has
+ * stopped; code, steps: n_seq x P; stats as above.  Each may be NULL (not all four).  FOTG_ERR_ARG also for P < 1 and a null pts. */
+int fotg_track_points(int device, int n_seq, int T, const float *flows, const float *flows_bw, int w, int h, float alpha1,
+                      float alpha2, int P, const float *pts, float *traj, unsigned char *code, int *steps, unsigned long long *stats,
+                      void *stream);
+/* The same along T coarse flows of a context (T x hl x wl x 2, the outflow of fotg_calc_sequence; coarse_bw that of
+ * fotg_calc_sequence_bidir, or NULL), upsampled and cropped on the fly: the batch index is the step, the T flows form one sequence
+ * of h_org x w_org frames.  Every output equals the dense form run on fotg_upsample_crop's outputs byte for byte, without writing a
+ * full-resolution flow.  FOTG_ERR_ARG also for T > max_batch and a depth-mode context. */
+int fotg_upsample_crop_flow_chain(fotg_ctx *ctx, int T, const float *coarse_flows, const float *coarse_bw, float alpha1, float alpha2,
+                                  float *total, unsigned char *code, int *steps, unsigned long long *stats, void *stream);
+int fotg_upsample_crop_track_points(fotg_ctx *ctx, int T, const float *coarse_flows, const float *coarse_bw, float alpha1,
+                                    float alpha2, int P, const float *pts, float *traj, unsigned char *code, int *steps,
+                                    unsigned long long *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
