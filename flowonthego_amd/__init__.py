@@ -24,6 +24,13 @@ def __getattr__(name):
     if name in ("chain", "track_points", "upsample_crop_chain", "upsample_crop_track_points"):
         import importlib
         return getattr(importlib.import_module(".chain", __name__), name)
+    if name in ("motion_flow", "upsample_crop_fit_motion", "smoothing_motions", "MODELS", "CODES"):
+        from . import motion
+        return getattr(motion, name)
+    if name in ("fit_motion", "stabilize"):
+        # (the command-line modules of these names; each is callable as the function of flowonthego_amd.motion)
+        import importlib
+        return importlib.import_module("." + name, __name__)
     if name in ("interpolate", "upsample_crop_interpolate"):
         from . import interp
         return getattr(interp, name)

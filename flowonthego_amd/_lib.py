@@ -81,6 +81,10 @@ SYMBOLS = [
     ("fotg_track_points", C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp]),
     ("fotg_upsample_crop_flow_chain", C.c_int, [vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     ("fotg_upsample_crop_track_points", C.c_int, [vp, C.c_int, vp, vp, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp]),
+    ("fotg_fit_motion", C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_fit_motion", C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_motion_flow", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]),
+    ("fotg_motion_ending", C.c_int, [C.c_int]),
     ("fotg_level_size", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_out_size", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_num_patches", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -267,6 +267,25 @@ class OFClass:
         from .chain import track
         return track(self, frames, points=points, alpha1=alpha1, alpha2=alpha2, stats=stats, fused=fused)
 
+    def upsample_crop_fit_motion(self, flow, mask=None, model="affine", iters=3, thresh=1.0, code=False, residual=False, stats=False,
+                                 sums=False, fused=None):
+        """the camera motion that explains upsample_crop(flow), and the pixels that do not follow it -- flowonthego_amd.motion"""
+        from .motion import upsample_crop_fit_motion
+        return upsample_crop_fit_motion(self, flow, mask, model=model, iters=iters, thresh=thresh, code=code, residual=residual,
+                                        stats=stats, sums=sums, fused=fused)
+
+    def camera_motion(self, frames, model="affine", iters=3, thresh=1.0, fused=None):
+        """the flows of frames (T+1, ...) and the motion fitted to each: (T, 6) float64, occluded pixels left out on a bidir context
+        -- flowonthego_amd.motion"""
+        from .motion import camera_motion
+        return camera_motion(self, frames, model=model, iters=iters, thresh=thresh, fused=fused)
+
+    def stabilize(self, frames, model="similarity", radius=15, fill=None, stats=False, iters=3, thresh=1.0):
+        """the flows of frames (T+1, ...), their camera path, and the frames resampled along the smoothed path: (frames, codes[,
+        statistics]) -- flowonthego_amd.motion.stabilize"""
+        from .motion import ofc_stabilize
+        return ofc_stabilize(self, frames, model=model, radius=radius, fill=fill, stats=stats, iters=iters, thresh=thresh)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

@@ -1,0 +1,68 @@
+"""python -m flowonthego_amd.stabilize frames.npy out.npy [--model translation|similarity|affine] [--radius N] [--op-point K]
+                                       [--fill V]
+
+Stabilises a video on the GPU: frames.npy holds a (T+1, h, w) or (T+1, h, w, 3) uint8 or float32 array.  The flows of the sequence
+are computed (both directions, so that occluded pixels stay out of the fit), a camera motion is fitted to each, the camera path is
+smoothed over --radius frames to either side and every frame resampled along the smoothed path (OFClass.stabilize).  out.npy gets
+the stabilised frames, same shape and type.  --fill V: pixels the resampling cannot fill get V instead of the border's colour.
+Prints the share of such pixels per frame.
+
+The module is callable: flowonthego_amd.stabilize(frames, flows, ...) is flowonthego_amd.motion.stabilize(frames, flows, ...)."""
+import argparse
+import sys
+import types
+
+
+def main(argv=None):
+    from .motion import MODELS
+    ap = argparse.ArgumentParser(prog="stabilize", description=__doc__.splitlines()[0])
+    ap.add_argument("frames")
+    ap.add_argument("out")
+    ap.add_argument("--model", default="similarity", choices=MODELS)
+    ap.add_argument("--radius", type=int, default=15)
+    ap.add_argument("--op-point", type=int, default=2)
+    ap.add_argument("--fill", type=float, default=None)
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if a.radius < 0:
+        ap.error("--radius must be >= 0")
+    import numpy as np
+    import torch
+    from . import img_params, operating_point
+    from .oflow import OFClass
+    try:
+        frames = np.load(a.frames)
+    except (OSError, ValueError) as e:
+        sys.stderr.write("stabilize: %s\n" % e)
+        return 1
+    if frames.ndim not in (3, 4) or frames.shape[0] < 2 or frames.dtype not in (np.uint8, np.float32) or (frames.ndim == 4 and frames.shape[3] not in (1, 3)):
+        sys.stderr.write("stabilize: %s must hold a (T+1, h, w) or (T+1, h, w, 3) uint8 or float32 array, T >= 1\n" % a.frames)
+        return 1
+    if frames.ndim == 4 and frames.shape[3] == 1:
+        frames = frames[..., 0]
+    T, h, w = frames.shape[0] - 1, frames.shape[1], frames.shape[2]
+    color = frames.ndim == 4
+    u8_rgb = color and frames.dtype == np.uint8          # 8-bit colour frames become gray on load; float32 ones are used as RGB
+    op = operating_point(a.op_point, w, 3 if color and not u8_rgb else 1)
+    op.bidir = True
+    if u8_rgb:
+        op.u8_color = 2
+    ofc = OFClass(op, img_params(width=w, height=h), max_batch=T)
+    out, code = ofc.stabilize(torch.from_numpy(np.ascontiguousarray(frames)).cuda(), model=a.model, radius=a.radius, fill=a.fill)
+    np.save(a.out, out.cpu().numpy())
+    holes = (code != 0).float().mean(dim=(1, 2)).cpu().numpy()
+    print("unfilled share per frame: " + " ".join("%.4f" % v for v in holes))
+    ofc.close()
+    return 0
+
+
+class _Callable(types.ModuleType):
+    """importing this submodule binds the package attribute `stabilize` to the module: calling it calls motion.stabilize()"""
+    def __call__(self, *a, **kw):
+        from .motion import stabilize
+        return stabilize(*a, **kw)
+
+
+sys.modules[__name__].__class__ = _Callable
+
+if __name__ == "__main__":
+    sys.exit(main())

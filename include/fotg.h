@@ -434,6 +434,54 @@ int fotg_upsample_crop_track_points(fotg_ctx *ctx, int T, const float *coarse_fl
                                     float alpha2, int P, const float *pts, float *traj, unsigned char *code, int *steps,
                                     unsigned long long *stats, void *stream);
 
+/* ---- global motion: the one camera motion that explains a flow, and the pixels that do not follow it, csrc/motion.hip.h -------
+ * A robust least-squares fit of u = a00 x + a01 y + tx, v = a10 x + a11 y + ty (x, y in pixels of the w x h image) to a flow.
+ * model: 0 translation (A = 0), 1 similarity (a00 = a11, a01 = -a10), 2 affine.  In order:
+ * Per pixel, integers and f32: X = 2x - (w-1), Y = 2y - (h-1); known = |u| <= 4096 && |v| <= 4096 (false for a NaN or an
+ * infinity); U = (int)rintf(u * 256), V = (int)rintf(v * 256) (exact for a known pixel); admissible = known and mask == 0.
+ * Round r = 0 .. iters selects the admissible pixels (r = 0) or those of them that follow the previous round's parameters (r > 0)
+ * and reduces twelve int64 sums over them: n, sum X, Y, XX, XY, YY, U, XU, YU, V, XV, YV.  For w, h <= 16384 none can overflow
+ * (|sum XU| <= 2^28 x 2^14 x 2^20 = 2^62); integer addition is associative, so the sums are the same bits whatever the order.
+ * Solve, f64, every operation rounded on its own, for U ~ c0 X + c1 Y + c2, V ~ c3 X + c4 Y + c5:
+ *   translation (n >= 1):  c2 = SU / n;  c5 = SV / n
+ *   similarity (n >= 2):   D = n (SXX + SYY) - (SX SX + SY SY) > 0;  a = (n (SXU + SYV) - (SX SU + SY SV)) / D;
+ *                          b = (n (SXV - SYU) - (SX SV - SY SU)) / D;  c0 = c4 = a;  c3 = b;  c1 = -b;
+ *                          c2 = ((SU - a SX) + b SY) / n;  c5 = ((SV - b SX) - a SY) / n
+ *   affine (n >= 3):       A00 = SYY n - SY SY;  A01 = SX SY - SXY n;  A02 = SXY SY - SYY SX;  A11 = SXX n - SX SX;
+ *                          A12 = SX SXY - SXX SY;  A22 = SXX SYY - SXY SXY;  det = (SXX A00 + SXY A01) + SX A02 > 0;
+ *                          c0 = ((A00 SXU + A01 SYU) + A02 SU) / det;  c1 = ((A01 SXU + A11 SYU) + A12 SU) / det;
+ *                          c2 = ((A02 SXU + A12 SYU) + A22 SU) / det;  c3 .. c5 alike with SXV, SYV, SV
+ *   to the pixel frame, per row:  q_i = c_i / 256;  a_0 = 2 q0;  a_1 = 2 q1;  t = (q2 - q0 (double)(w-1)) - q1 (double)(h-1)
+ * A round whose system is unusable keeps the previous parameters (zeros before round 0) and clears `fitted` for good.
+ * Prediction, f32, every operation rounded on its own, per row of the six f64 parameters: h0 = a_0 / 2; h1 = a_1 / 2;
+ * k0 = (float)h0; k1 = (float)h1; k2 = (float)((t + h0 (double)(w-1)) + h1 (double)(h-1));  pu = (k0 (float)X + k1 (float)Y) + k2.
+ * du = u - pu; dv = v - pv; a pixel follows the model iff du du + dv dv <= thresh thresh.
+ * flow: n x h x w x 2 f32; mask: NULL or n x h x w uint8 in the alphabet of the consistency check (only code-0 pixels take part);
+ * iters 0 .. 64; thresh >= 0, in pixels.  Outputs on the device, each but params may be NULL:
+ *   params   n x 6 f64  [a00 a01 tx a10 a11 ty]
+ *   code     n x h x w uint8: 0 follows the model, 1 does not (independent motion), 2 excluded by the mask, 3 unknown
+ *   residual n x h x w x 2 f32: (du, dv) against the final parameters
+ *   stats    n x 6 int64: pixels of code 0, 1, 2, 3, pixels in the last fit, fitted (1: every round's system was usable)
+ *   sums     n x 12 int64: the last round's sums
+ * code, residual and the counts come from one final pass, skipped when none of them is asked for.  Asynchronous on `stream`; the
+ * parameters never leave the device between rounds.  FOTG_ERR_ARG: n < 1 (or > 65535), w or h < 1 or > 16384, a model, iters or
+ * thresh out of range, a null flow or params, an output overlapping an input or another output. */
+int fotg_fit_motion(int device, int n, const float *flow, const unsigned char *mask, int w, int h, int model, int iters, float thresh,
+                    double *params, unsigned char *code, float *residual, long long *stats, long long *sums, void *stream);
+/* The same on the coarse flow of a context (n x hl x wl x 2), upsampled and cropped on the fly; mask at the original size.  Every
+ * output equals the dense fit of fotg_upsample_crop's output byte for byte.  FOTG_ERR_ARG also for n > max_batch and a depth-mode
+ * context. */
+int fotg_upsample_crop_fit_motion(fotg_ctx *ctx, int n, const float *coarse_flow, const unsigned char *mask, int model, int iters,
+                                  float thresh, double *params, unsigned char *code, float *residual, long long *stats, long long *sums,
+                                  void *stream);
+/* The model as a flow: params n x 6 f64 -> flow n x h x w x 2 f32, (pu, pv) of the prediction above, so that a flow minus it is the
+ * fit's residual bit for bit.  FOTG_ERR_ARG: n < 1 (or > 65535), w or h < 1, a null pointer, flow overlapping params. */
+int fotg_motion_flow(int device, int n, const double *params, int w, int h, float *flow, void *stream);
+/* How a pass's sums reach the accumulators: 0 one 64-bit integer atomic per workgroup and sum, 1 per-workgroup partials folded
+ * by a second launch.  The results are the same bits; this exists to time both.  Sets the process-wide ending for later
+ * calls (any other value only queries) and returns the previous one. */
+int fotg_motion_ending(int ending);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,

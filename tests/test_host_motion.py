@@ -1,0 +1,118 @@
+"""The global-motion fit's host side (no GPU needed): the C-ABI is declared and bound, examples/fit_motion.cpp compiles and links
+against the C++ shim, the two command-line tools refuse bad arguments, and the compiler's resource table lists every instantiation
+of the motion kernels without a private-memory segment."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+
+from conftest import ROOT
+
+NEW_SYMBOLS = ("fotg_fit_motion", "fotg_upsample_crop_fit_motion", "fotg_motion_flow", "fotg_motion_ending")
+
+
+def test_entry_points_are_declared_bound_and_exported():
+    import flowonthego_amd as F
+    from flowonthego_amd._lib import SYMBOLS
+    L = F.lib()
+    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
+    bound = {s[0]: s for s in SYMBOLS}
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\bint %s\(" % name, hdr), name
+        assert name in bound and hasattr(L, name)
+        # one ctypes argument per parameter of the declaration
+        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
+        assert len(decl.split(",")) == len(bound[name][2]), name
+    shim = open(os.path.join(ROOT, "include", "fotg", "motion.h")).read()
+    for name in NEW_SYMBOLS[:3]:
+        assert name + "(" in shim
+    for name in ("fit_motion", "motion_flow", "upsample_crop_fit_motion", "stabilize", "smoothing_motions"):
+        assert callable(getattr(F, name)), name
+    assert F.MODELS == ("translation", "similarity", "affine") and len(F.CODES) == 4
+    import flowonthego_amd.motion as M
+    for name in ("fit_motion", "motion_flow", "stabilize", "MODELS", "CODES"):
+        assert hasattr(M, name), name
+    from flowonthego_amd.oflow import OFClass
+    for name in ("upsample_crop_fit_motion", "camera_motion", "stabilize"):
+        assert callable(getattr(OFClass, name)), name
+    # the definition and the overflow limit of the sums are written at the head of the kernels and in the public header
+    head = open(os.path.join(ROOT, "flowonthego_amd", "csrc", "motion.hip.h")).read()
+    for text in (head, hdr):
+        assert "2^62" in text and "16384" in text
+
+
+def test_the_ending_switch_needs_no_gpu():
+    import flowonthego_amd as F
+    L = F.lib()
+    first = L.fotg_motion_ending(-1)
+    assert first in (0, 1)
+    assert L.fotg_motion_ending(1 - first) == first and L.fotg_motion_ending(7) == 1 - first
+    assert L.fotg_motion_ending(first) == 1 - first and L.fotg_motion_ending(-1) == first
+
+
+def test_fit_motion_example_builds(tmp_path):
+    import flowonthego_amd as F
+    F.lib()
+    from test_host import _build_example
+    exe = _build_example(tmp_path, "fit_motion")
+    assert os.path.exists(exe)
+    for args in ([], ["a.flo", "projective"], ["a.flo", "affine", "x"]):
+        r = subprocess.run([exe] + args, capture_output=True, text=True)
+        assert r.returncode != 0 and "usage" in r.stderr, args
+
+
+def test_cli_argument_errors(tmp_path):
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    bad = {"fit_motion": ([], ["a.flo", "b.flo"], ["a.flo", "--model", "projective"], ["a.flo", "--iters", "-1"], ["a.flo", "--thresh", "-2"],
+                          ["a.flo", "--mask"]),
+           "stabilize": ([], ["frames.npy"], ["frames.npy", "out.npy", "--model", "homography"], ["frames.npy", "out.npy", "--radius", "-1"],
+                         ["frames.npy", "out.npy", "extra.npy"])}
+    for tool, cases in bad.items():
+        for args in cases:
+            r = subprocess.run([sys.executable, "-m", "flowonthego_amd." + tool] + args, capture_output=True, text=True, cwd=ROOT, env=env)
+            assert r.returncode != 0 and "usage" in r.stderr, (tool, args)
+
+
+def test_gray_png_reader_reads_every_filter(tmp_path):
+    """the mask reader of the fit_motion tool against a PNG written here with each of the five row filters"""
+    import struct
+    import zlib
+    from flowonthego_amd.fit_motion import read_gray_png
+    rng = np.random.default_rng(2)
+    img = rng.integers(0, 256, (10, 7), dtype=np.uint8)
+    img[:, 3] = 0
+    rows, prev = [], np.zeros(7, np.int32)
+    for y in range(10):
+        ft, cur, line = y % 5, img[y].astype(np.int32), []
+        for x in range(7):
+            a, b, c = (cur[x - 1] if x else 0), prev[x], (prev[x - 1] if x else 0)
+            pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
+            paeth = a if pa <= pb and pa <= pc else (b if pb <= pc else c)
+            line.append((cur[x] - (0, a, b, (a + b) // 2, paeth)[ft]) & 255)
+        rows.append(bytes([ft] + line))
+        prev = cur
+    chunk = lambda tag, data: struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+    path = str(tmp_path / "m.png")
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", 7, 10, 8, 0, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(b"".join(rows))) + chunk(b"IEND", b""))
+    assert np.array_equal(read_gray_png(path), img)
+
+
+def test_resource_table_lists_the_motion_kernels_without_scratch():
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
+    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
+    names = re.findall(r"Function Name: (\S+)", txt)
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
+    assert len(names) == len(scratch)
+    table = dict(zip(names, scratch))
+    # Itanium-mangled: motion_pass_kernel<DenseSrc | UpsampleSrc, round 0 | later round | final>, motion_fold_kernel<12 | 4>
+    want = ["motion_pass_kernelI%sLi%dE" % (src, p) for src in ("NS_8DenseSrcE", "NS_11UpsampleSrcE") for p in (0, 1, 2)]
+    want += ["motion_fold_kernelILi12E", "motion_fold_kernelILi4E", "motion_solve_kernelE", "motion_flow_kernelE"]
+    for w in want:
+        hit = [n for n in names if w in n]
+        assert len(hit) == 1, w
+        assert table[hit[0]] == 0, hit
+    assert len([n for n in names if "motion_" in n]) == len(want)                  # and no instantiation beyond these
