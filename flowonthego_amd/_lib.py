@@ -49,6 +49,9 @@ SYMBOLS = [
     ("fotg_pipe_sync", C.c_int, [vp]),
     ("fotg_pipe_ticket_event", C.c_int, [vp, C.c_long, C.POINTER(vp)]),
     ("fotg_pipe_context", C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    ("fotg_pipe_probe_overlap", C.c_int, [vp, f32p]),
+    ("fotg_pipe_queue_info", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), f32p]),
+    ("fotg_pipe_slot_priority", C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
     ("fotg_node_create", C.c_int, [C.POINTER(FotgParams), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
     ("fotg_node_destroy", None, [vp]),
     ("fotg_node_shard", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

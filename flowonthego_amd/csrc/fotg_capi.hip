@@ -13,6 +13,7 @@
 #include <type_traits>
 #include "common.h"
 #include "pipe_tickets.h"
+#include "pipe_queues.h"
 #include "pyramid.hip.h"
 #include "lk.hip.h"
 #include "lk_fast.hip.h"
@@ -86,7 +87,8 @@ struct FotgTune {
   int lk_lpp_min_waves;   // FOTG_LK_LPP_MIN_WAVES: automatic: eight lanes per patch from this many waves per launch on
   int test_taps;    // FOTG_TEST_TAPS: 1 = fotg_ctx_counter(ctx, "inject_stall") is live (tests of the FOTG_ERR_STALL reporting)
 };
-static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+static const char *env_str(const char *name) { return getenv(name); }
+static int env_int(const char *name, int dflt) { const char *e = env_str(name); return e ? atoi(e) : dflt; }
 
 #ifdef FOTG_DEBUG
 static std::map<void *, void *> g_dbg_base;      // user pointer -> allocation base (FOTG_DEBUG_GUARD)
@@ -1541,8 +1543,88 @@ struct fotg_pipe {
   struct Args { int n, u8; const void *I0, *I1; const float *initflow; float *out; } args[4 * FOTG_PIPE_MAX_DEPTH];
   fotg_tickets::PipeBook book;                       // which tickets are healable / suspects / stalled, and what a wait reports (pipe_tickets.h)
   long healed;                                       // batches recomputed so far
+  // where the slot streams live (pipe_queues.h): the hardware-queue budget read at creation, the layout in use, the device's
+  // priority range and the width the last overlap probe measured (0: none has run)
+  int q_budget, q_layout, prio_least, prio_greatest;
+  float q_width;
   std::mutex *mu;                                    // submit / verification (fotg_node waits from another thread than the one that submits)
 };
+
+}  // extern "C"
+// The overlap probe's kernel: holds its workgroup for `ticks` of the 100 MHz wall clock or `cap` rounds of s_sleep, whichever ends
+// first.  It reads and writes no memory, so there is nothing it could wait for.
+__global__ void pipe_spin_kernel(long ticks, int cap)
+{
+  const long t0 = wall_clock64();
+  for (int i = 0; i < cap && wall_clock64() - t0 < ticks; ++i) __builtin_amdgcn_s_sleep(8);
+}
+extern "C" {
+
+static void pipe_drop_streams(fotg_pipe *q)
+{
+  for (int k = 0; k < q->depth; ++k)
+    if (q->stream[k]) { (void)hipStreamSynchronize(q->stream[k]); (void)hipStreamDestroy(q->stream[k]); q->stream[k] = nullptr; }
+}
+
+// The slot streams of a pipe under `layout`, created back to back so that the runtime deals them to consecutive hardware queues of
+// their pool; all non-blocking.  The normal layout is exactly the streams the pipe always had.
+static int pipe_make_streams(fotg_pipe *q, int layout, fotg_queues::Plan *plan)
+{
+  const fotg_queues::Plan pl = fotg_queues::place(layout, q->q_budget, q->depth, q->prio_least, q->prio_greatest);
+  for (int k = 0; k < q->depth; ++k) {
+    const hipError_t e = pl.cls[k] == fotg_queues::CLS_NORMAL
+                             ? hipStreamCreateWithFlags(&q->stream[k], hipStreamNonBlocking)
+                             : hipStreamCreateWithPriority(&q->stream[k], hipStreamNonBlocking,
+                                                           fotg_queues::priority_of(pl.cls[k], q->prio_least, q->prio_greatest));
+    if (e != hipSuccess) { g_last_hip = (int)e; q->stream[k] = nullptr; pipe_drop_streams(q); return FOTG_ERR_HIP; }
+  }
+  q->q_layout = pl.layout;
+  if (plan) *plan = pl;
+  return FOTG_OK;
+}
+
+// tools/queue_probe.hip's shape, bounded: kProbeLaunches dependent launches on every slot stream (round robin, as submits arrive),
+// then on slot 0 alone, timed by events on the streams themselves.  Called with the pipe's mutex held (or before the pipe is out).
+static int pipe_probe(fotg_pipe *q, float *width)
+{
+  constexpr int kProbeLaunches = 8, kProbeCap = 4096;        // (4096 rounds of s_sleep 8: under a millisecond per launch at any clock)
+  // about 30 us per launch; 60 us for more than four slots, where the host needs longer than 30 us to launch one round
+  const long ticks = q->depth > 4 ? 6000 : 3000;
+  if (q->depth == 1) { *width = 1.f; return FOTG_OK; }
+  hipEvent_t ev[2 * FOTG_PIPE_MAX_DEPTH] = {};
+  int st = FOTG_OK;
+  auto fail = [&](hipError_t e) { if (e != hipSuccess && st == FOTG_OK) { g_last_hip = (int)e; st = FOTG_ERR_HIP; } return e != hipSuccess; };
+  for (int k = 0; k < 2 * q->depth && st == FOTG_OK; ++k) fail(hipEventCreate(&ev[k]));
+  float t_alone = 0.f, t_together = 0.f;
+  if (st == FOTG_OK) {
+    // code object and queues warm, every stream drained
+    for (int k = 0; k < q->depth; ++k) pipe_spin_kernel<<<64, 64, 0, q->stream[k]>>>(1, 1);
+    fail(hipGetLastError());
+    for (int k = 0; k < q->depth; ++k) fail(hipStreamSynchronize(q->stream[k]));
+  }
+  for (int pass = 0; pass < 2 && st == FOTG_OK; ++pass) {
+    const int ns = pass == 0 ? q->depth : 1;
+    for (int k = 0; k < ns; ++k) fail(hipEventRecord(ev[2 * k], q->stream[k]));
+    for (int m = 0; m < kProbeLaunches; ++m)
+      for (int k = 0; k < ns; ++k) pipe_spin_kernel<<<64, 64, 0, q->stream[k]>>>(ticks, kProbeCap);
+    fail(hipGetLastError());
+    for (int k = 0; k < ns; ++k) fail(hipEventRecord(ev[2 * k + 1], q->stream[k]));
+    for (int k = 0; k < ns; ++k) fail(hipStreamSynchronize(q->stream[k]));
+    // from the earliest start to the latest end
+    float first = 0.f, last = 0.f;
+    for (int k = 0; k < ns && st == FOTG_OK; ++k) {
+      float a = 0.f, b = 0.f;
+      if (fail(hipEventElapsedTime(&a, ev[0], ev[2 * k])) || fail(hipEventElapsedTime(&b, ev[0], ev[2 * k + 1]))) break;
+      first = a < first ? a : first;
+      last = b > last ? b : last;
+    }
+    (pass == 0 ? t_together : t_alone) = last - first;
+  }
+  for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+  if (st != FOTG_OK) return st;
+  *width = t_together > 0.f ? q->depth * t_alone / t_together : 0.f;
+  return FOTG_OK;
+}
 
 void fotg_pipe_destroy(fotg_pipe *q)
 {
@@ -1552,8 +1634,8 @@ void fotg_pipe_destroy(fotg_pipe *q)
     if (q->stream[k]) (void)hipStreamSynchronize(q->stream[k]);
     if (q->ctx[k]) fotg_destroy(q->ctx[k]);
     if (q->ready[k]) (void)hipEventDestroy(q->ready[k]);
-    if (q->stream[k]) (void)hipStreamDestroy(q->stream[k]);
   }
+  pipe_drop_streams(q);
   for (auto &e : q->done) if (e) (void)hipEventDestroy(e);
   delete q->mu;
   delete q;
@@ -1562,27 +1644,76 @@ void fotg_pipe_destroy(fotg_pipe *q)
 int fotg_pipe_create(const fotg_params *p, int w_org, int h_org, int device, int max_batch, int depth, fotg_pipe **out)
 {
   if (!out || depth < 1 || depth > FOTG_PIPE_MAX_DEPTH) return FOTG_ERR_ARG;
-  ON_DEVICE(device);
-  {
-    // HIP deals its streams to GPU_MAX_HW_QUEUES hardware queues (default 4, the null stream included) and two busy streams on
-    // one queue run one after the other: more than three slots need the variable set BEFORE the HIP runtime is loaded
-    // (INTEGRATION.md section 4).  The library cannot set it any more at this point; say so once.
-    static std::atomic<bool> warned{false};
-    if (depth > 3 && env_int("GPU_MAX_HW_QUEUES", 4) < depth + 1 && !warned.exchange(true))      // (creation time, not the launch path)
-      fprintf(stderr, "fotg_pipe_create: %d batches in flight need a hardware queue each (+ one for the null stream): GPU_MAX_HW_QUEUES "
-                      "must be >= %d in the environment BEFORE libamdhip64 is loaded (a setenv after that is not seen by the runtime, and "
-                      "not by this check either); otherwise slots share queues and do not overlap\n", depth, depth + 1);
+  // FOTG_PIPE_QUEUES=auto|normal|high|split: read once here, like the other FOTG_PIPE_* switches (creation time, not the launch path)
+  const int mode = fotg_queues::parse_mode(env_str("FOTG_PIPE_QUEUES"));
+  if (mode == fotg_queues::MODE_BAD) {
+    fprintf(stderr, "fotg_pipe_create: FOTG_PIPE_QUEUES must be auto, normal, high or split\n");
+    return FOTG_ERR_ARG;
   }
+  ON_DEVICE(device);
   fotg_pipe *q = new (std::nothrow) fotg_pipe();          // (value-initialised: every handle and counter starts at zero)
   if (!q) return FOTG_ERR_ARG;
   q->device = device; q->depth = depth; q->nring = 4 * depth;
   q->book = fotg_tickets::PipeBook(depth);
   q->mu = new (std::nothrow) std::mutex();
   if (!q->mu) { delete q; return FOTG_ERR_ARG; }
-  // the slots' streams first and back to back, so that the runtime spreads them over its hardware queues
+  // HIP deals its streams to GPU_MAX_HW_QUEUES hardware queues PER STREAM PRIORITY (default 4; the normal pool also carries the null
+  // stream and whatever streams the rest of the process creates), and two busy streams on one queue run one after the other.  The
+  // variable is read by the runtime when it is loaded; the library neither sets it nor asks for more than it finds.  With a queue per
+  // slot and one to spare (budget >= depth + 1) the slots stay at normal priority, as they always were; below that they go to the
+  // high-priority pool, which nobody else draws from (pipe_queues.h), so depth <= 8 needs no variable at the default budget.
+  q->q_budget = env_int("GPU_MAX_HW_QUEUES", 4);
+  if (hipDeviceGetStreamPriorityRange(&q->prio_least, &q->prio_greatest) != hipSuccess) {
+    g_last_hip = (int)hipGetLastError();
+    fotg_pipe_destroy(q);
+    return FOTG_ERR_HIP;
+  }
+  // the slots' streams first and back to back, so that the runtime spreads them over the hardware queues of their pool
+  fotg_queues::Plan plan;
+  int st = pipe_make_streams(q, mode == fotg_queues::MODE_AUTO ? fotg_queues::auto_layout(q->q_budget, depth) : mode, &plan);
+  if (st != FOTG_OK) { fotg_pipe_destroy(q); return st; }
+  if (mode == fotg_queues::MODE_AUTO && depth > 1) {
+    // Nobody can see which queue a stream got, and a pipe created after other streams does not follow any simple dealing rule: measure.
+    // A layout whose slots do not overlap (width < 0.75 * depth) is dropped -- its streams destroyed before the next ones are
+    // created -- for the remaining layouts in the order high, split, normal; the widest stays.  A few milliseconds, here only.
+    // (Depth counts up to four there: the chip does not run more than four to five queues' probe kernels at once -- 4.6 wide at
+    // depth 6 and 5.1 - 5.4 at depth 8 with a queue per slot, docs/EXPERIMENTS.md -- so 0.75 * depth is out of reach for deeper pipes
+    // on any layout and would reshuffle them by noise, also at budgets where the normal layout has always been right.)
+    const float enough = 0.75f * (depth < 4 ? depth : 4);
+    st = pipe_probe(q, &q->q_width);
+    int tried[4] = {q->q_layout, -1, -1, -1}, ntried = 1, best = q->q_layout, order[3];
+    float best_width = q->q_width;
+    const int norder = fotg_queues::fallback_order(q->q_layout, order);
+    for (int i = 0; i < norder && st == FOTG_OK && q->q_width < enough; ++i) {
+      const int eff = fotg_queues::place(order[i], q->q_budget, depth, q->prio_least, q->prio_greatest).layout;
+      bool seen = false;
+      for (int j = 0; j < ntried; ++j) seen = seen || tried[j] == eff;       // (a device without the pool: the same streams again)
+      if (seen) continue;
+      tried[ntried++] = eff;
+      pipe_drop_streams(q);
+      st = pipe_make_streams(q, order[i], &plan);
+      if (st == FOTG_OK) st = pipe_probe(q, &q->q_width);
+      if (st == FOTG_OK && q->q_width > best_width) { best_width = q->q_width; best = q->q_layout; }
+    }
+    if (st == FOTG_OK && q->q_layout != best) {          // none was wide enough and the last one tried is not the widest
+      pipe_drop_streams(q);
+      st = pipe_make_streams(q, best, &plan);
+      if (st == FOTG_OK) st = pipe_probe(q, &q->q_width);
+    }
+    if (st != FOTG_OK) { fotg_pipe_destroy(q); return st; }
+  }
+  {
+    static std::atomic<bool> warned{false};
+    if (plan.shared && !warned.exchange(true))
+      fprintf(stderr, "fotg_pipe_create: %d batches in flight, %d hardware queues per stream priority (GPU_MAX_HW_QUEUES in the "
+                      "environment when libamdhip64 was loaded; default 4): %d / %d / %d slot streams at high / low / normal priority "
+                      "(the normal pool also carries the null stream) -- more slot streams than queues in a pool: the device's priority "
+                      "pools together cannot give every slot a queue of its own (or FOTG_PIPE_QUEUES keeps the slots out of them), and "
+                      "slots that share a queue do not overlap\n",
+              depth, q->q_budget, plan.count[fotg_queues::CLS_HIGH], plan.count[fotg_queues::CLS_LOW], plan.count[fotg_queues::CLS_NORMAL]);
+  }
   for (int k = 0; k < depth; ++k)
-    if (hipStreamCreateWithFlags(&q->stream[k], hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&q->ready[k], hipEventDisableTiming) != hipSuccess) {
+    if (hipEventCreateWithFlags(&q->ready[k], hipEventDisableTiming) != hipSuccess) {
       g_last_hip = (int)hipGetLastError();
       fotg_pipe_destroy(q);
       return FOTG_ERR_HIP;
@@ -1594,7 +1725,7 @@ int fotg_pipe_create(const fotg_params *p, int w_org, int h_org, int device, int
       return FOTG_ERR_HIP;
     }
   for (int k = 0; k < depth; ++k) {
-    const int st = fotg_create(p, w_org, h_org, device, max_batch, &q->ctx[k]);
+    st = fotg_create(p, w_org, h_org, device, max_batch, &q->ctx[k]);
     if (st != FOTG_OK) { fotg_pipe_destroy(q); return st; }
     // several batches in flight: the base pyramid launch of a batch in up to 16 parts (pyramid_impl; measured 170 -> 181 k pairs/s
     // at batch 64 with four in flight, at the price of ~5 % on a batch that runs alone -- which is why only pipes do it)
@@ -1603,6 +1734,35 @@ int fotg_pipe_create(const fotg_params *p, int w_org, int h_org, int device, int
     if (depth > 1) q->ctx[k]->tune.lp_max_pairs = env_int("FOTG_PIPE_LEVELPIPE_MAX_PAIRS", 4 / depth > 1 ? 4 / depth : 1);
   }
   *out = q;
+  return FOTG_OK;
+}
+
+int fotg_pipe_probe_overlap(fotg_pipe *q, float *width)
+{
+  if (!q || !width) return FOTG_ERR_ARG;
+  std::lock_guard<std::mutex> lock(*q->mu);
+  if (q->book.outstanding()) return FOTG_ERR_ARG;         // (a batch may still be running on a slot: the probe would measure it, not the queues)
+  ON_DEVICE(q->device);
+  const int st = pipe_probe(q, width);
+  if (st == FOTG_OK) q->q_width = *width;
+  return st;
+}
+
+int fotg_pipe_queue_info(fotg_pipe *q, int *budget, int *layout, float *width)
+{
+  if (!q) return FOTG_ERR_ARG;
+  std::lock_guard<std::mutex> lock(*q->mu);
+  if (budget) *budget = q->q_budget;
+  if (layout) *layout = q->q_layout;
+  if (width) *width = q->q_width;
+  return FOTG_OK;
+}
+
+int fotg_pipe_slot_priority(fotg_pipe *q, int slot, int *priority)
+{
+  if (!q || !priority || slot < 0 || slot >= q->depth) return FOTG_ERR_ARG;
+  ON_DEVICE(q->device);
+  HIPCHK(hipStreamGetPriority(q->stream[slot], priority));
   return FOTG_OK;
 }
 

@@ -60,6 +60,16 @@ struct PipeBook {
   bool in_ring(long u) const { return u >= submitted - nring; }
   int slot(long u) const { return (int)(u % depth); }
 
+  // a submitted ticket that no host wait has settled yet (its batch may still be running)
+  bool outstanding() const
+  {
+    for (int k = 0; k < depth && k < submitted; ++k) {
+      const long last = submitted - 1 - (submitted - 1 - k) % depth;      // the slot's last ticket
+      if (last >= verified[k]) return true;
+    }
+    return false;
+  }
+
   // the ticket of the next submission; its ring entry is the one of ticket - nring, which is folded into its slot's lost set first
   // if it was stalled (its verdict must outlive the entry)
   long submit(bool healable_)

@@ -86,6 +86,26 @@ class FlowPipeline:
         Read-and-clear, does not synchronise."""
         return sum(int(lib().fotg_ctx_counter(self.context(k), b"take_stall")) for k in range(self.depth))
 
+    def queue_info(self):
+        """where the slot streams live (include/fotg.h, HARDWARE QUEUES): the hardware-queue budget read at creation, the layout
+        in use ("normal", "high" or "split"), the width the last overlap probe measured (0.0 if none has run) and the stream
+        priority of every slot as the runtime reports it (0 = normal, smaller = more urgent)"""
+        budget, layout, width, prio = C.c_int(), C.c_int(), C.c_float(), C.c_int()
+        check(lib().fotg_pipe_queue_info(self._h, budget, layout, width))
+        prios = []
+        for k in range(self.depth):
+            check(lib().fotg_pipe_slot_priority(self._h, k, prio))
+            prios.append(prio.value)
+        return {"budget": budget.value, "layout": ("normal", "high", "split")[layout.value], "width": width.value, "priorities": prios}
+
+    def probe_overlap(self):
+        """how many slots really run at once (fotg_pipe_probe_overlap: a short chain of spin kernels on every slot stream against the
+        same chain on one); about `depth` with a hardware queue per slot.  Raises FotgError while a submitted batch has not been
+        waited for by the host (wait(ticket, host=True) / synchronize())."""
+        width = C.c_float()
+        check(lib().fotg_pipe_probe_overlap(self._h, width))
+        return width.value
+
     def context(self, slot):
         h = C.c_void_p()
         check(lib().fotg_pipe_context(self._h, int(slot), h))

@@ -194,6 +194,32 @@ int fotg_pipe_sync(fotg_pipe *pipe);
 int fotg_pipe_ticket_event(fotg_pipe *pipe, long ticket, void **event);
 /* the engine context of a slot (geometry queries, taps, counters) */
 int fotg_pipe_context(fotg_pipe *pipe, int slot, fotg_ctx **ctx);
+/* HARDWARE QUEUES.  The HIP runtime deals the streams of a process to GPU_MAX_HW_QUEUES hardware queues (default 4) PER STREAM
+ * PRIORITY -- three pools: high, normal, low -- and two busy streams on one queue run one after the other.  The null stream and
+ * the streams of frameworks live in the normal pool.  fotg_pipe_create reads the budget from the environment (it sets nothing
+ * and asks for no more than it finds) and places its slot streams, FOTG_PIPE_QUEUES=auto|normal|high|split, read once at creation:
+ *   normal  every slot stream at normal priority: the choice of auto when the budget is >= depth + 1
+ *   high    up to `budget` slots in the highest-priority pool, further ones in the lowest-priority pool, the rest normal: the
+ *           choice of auto below that budget
+ *   split   slots alternate between the highest- and the lowest-priority pool
+ * With auto, creation then measures the layout it chose with fotg_pipe_probe_overlap and, if the width is below 0.75 * depth
+ * (depth counted up to 4: the probe's kernels of more than four to five queues do not run at once on any layout), tries the
+ * remaining layouts in the order high, split, normal and keeps the widest (a few milliseconds, at creation only).
+ * No variable needs to be set for depth <= 8; a warning is printed only when some pool still holds more slots than queues. */
+#define FOTG_PIPE_QUEUES_NORMAL 0
+#define FOTG_PIPE_QUEUES_HIGH   1
+#define FOTG_PIPE_QUEUES_SPLIT  2
+/* How many slots really run at once: a chain of 8 dependent launches of a spin kernel (64 workgroups of 64 threads, about 30 us
+ * each, bounded by an iteration cap: it waits on no memory) on every slot stream at once, then the same chain on slot 0 alone;
+ * *width = depth * t_alone / t_together, about `depth` with a queue per slot and about depth / 2 with two slots per queue.
+ * Synchronises the pipe's own streams only.  FOTG_ERR_ARG while a ticket has not been settled by a host wait (fotg_pipe_wait with
+ * host_wait != 0, or fotg_pipe_sync); such tickets and their results are left alone. */
+int fotg_pipe_probe_overlap(fotg_pipe *pipe, float *width);
+/* what creation read and chose (any pointer may be NULL): the budget, the layout (FOTG_PIPE_QUEUES_*) and the width of the last
+ * probe (0 if none has run: depth 1, or a layout forced through FOTG_PIPE_QUEUES) */
+int fotg_pipe_queue_info(fotg_pipe *pipe, int *budget, int *layout, float *width);
+/* the priority the runtime reports for a slot's stream (smaller = more urgent, 0 = normal) */
+int fotg_pipe_slot_priority(fotg_pipe *pipe, int slot, int *priority);
 
 /* ---- one process, several GPUs (no reference equivalent: src/run_dense.cpp:277-289 drives one device) ------------
  * Frame pairs are independent, so a batch of n pairs is cut into contiguous shards -- slot d gets the pairs [begin, begin + count)
