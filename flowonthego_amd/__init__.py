@@ -27,7 +27,10 @@ def __getattr__(name):
     if name in ("motion_flow", "upsample_crop_fit_motion", "smoothing_motions", "MODELS", "CODES"):
         from . import motion
         return getattr(motion, name)
-    if name in ("fit_motion", "stabilize"):
+    if name in ("label_components", "object_summary", "OBJECT", "OBJECT_STATS"):
+        from . import objects
+        return getattr(objects, name)
+    if name in ("fit_motion", "stabilize", "moving_objects"):
         # (the command-line modules of these names; each is callable as the function of flowonthego_amd.motion)
         import importlib
         return importlib.import_module("." + name, __name__)

@@ -88,6 +88,8 @@ SYMBOLS = [
     ("fotg_upsample_crop_fit_motion", C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
     ("fotg_motion_flow", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]),
     ("fotg_motion_ending", C.c_int, [C.c_int]),
+    ("fotg_label_components", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, C.c_int, vp, vp, vp, vp, vp]),
+    ("fotg_components_tile", C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_level_size", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_out_size", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_num_patches", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -1,0 +1,110 @@
+// fotg_components.hip -- C-ABI of the connected-component labelling (include/fotg.h fotg_label_components), kernels in
+// components.hip.h.  Per call seven launches on the caller's stream; the parent array (unless `labels` is asked for), the per-pixel
+// area array and the chunk counts are the call's own memory, taken from and returned to the stream's pool.  Nothing synchronises
+// with the host.
+#include "common.h"
+#include "components.hip.h"
+
+using namespace fotg;
+
+namespace {
+
+struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
+  int prev = -1;
+  bool ok = false;
+  hipError_t err = hipSuccess;
+  explicit DevGuard(int dev)
+  {
+    int cur = -1;
+    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
+    if (cur == dev) { ok = true; return; }
+    if ((err = hipSetDevice(dev)) != hipSuccess) return;
+    prev = cur; ok = true;
+  }
+  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+int hip_fail(hipError_t e)
+{
+  set_last_hip_error((int)e);
+  return FOTG_ERR_HIP;
+}
+
+struct Span { const void *p; size_t bytes; };
+
+bool overlap(const Span &a, const Span &b)
+{
+  if (!a.p || !b.p) return false;
+  const char *x = static_cast<const char *>(a.p), *y = static_cast<const char *>(b.p);
+  return x < y + b.bytes && y < x + a.bytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fotg_label_components(int device, int n, const unsigned char *code, int w, int h, int fg_codes, int connectivity,
+                          const float *values, long long min_area, int max_objects, int *labels, int *ids, long long *objects,
+                          long long *stats, void *stream_)
+{
+  if (n < 1 || n > 65535 || w < 1 || h < 1 || w > COMP_MAX_DIM || h > COMP_MAX_DIM || !code || !objects) return FOTG_ERR_ARG;
+  if (fg_codes < 1 || fg_codes > 255 || (connectivity != 4 && connectivity != 8)) return FOTG_ERR_ARG;
+  if (min_area < 1 || max_objects < 1 || max_objects > COMP_MAX_OBJECTS) return FOTG_ERR_ARG;
+  const size_t hw = (size_t)w * h;
+  const int ntx = (w + COMP_TW - 1) / COMP_TW, nty = (h + COMP_TH - 1) / COMP_TH;
+  const int chunks = (int)((hw + COMP_CHUNK - 1) / COMP_CHUNK);                     // <= 2^18
+  const size_t tiles = (size_t)ntx * nty * n;
+  if (tiles > 0x7fffffffUL) return FOTG_ERR_ARG;
+  const Span out[4] = {{labels, n * hw * 4}, {ids, n * hw * 4}, {objects, (size_t)n * max_objects * COMP_NREC * 8},
+                       {stats, (size_t)n * COMP_NSTAT * 8}};
+  const Span in[2] = {{code, n * hw}, {values, n * hw * 8}};
+  for (int i = 0; i < 4; ++i) {
+    for (int j = 0; j < 2; ++j)
+      if (overlap(out[i], in[j])) return FOTG_ERR_ARG;
+    for (int j = i + 1; j < 4; ++j)
+      if (overlap(out[i], out[j])) return FOTG_ERR_ARG;
+  }
+  DevGuard guard(device);
+  if (!guard.ok) return hip_fail(guard.err);
+  hipStream_t stream = (hipStream_t)stream_;
+  // the call's memory: [the parents, n h w] the areas, n h w; the chunk counts, n chunks
+  const size_t ints = (labels ? 0 : n * hw) + n * hw + (size_t)n * chunks;
+  int *ws = nullptr;
+  hipError_t e = hipMallocAsync((void **)&ws, ints * sizeof(int), stream);
+  if (e != hipSuccess) return hip_fail(e);
+  int *par = labels ? labels : ws;
+  int *aux = labels ? ws : ws + n * hw;
+  int *chunk_cnt = aux + n * hw;
+  e = hipMemsetAsync(objects, 0, out[2].bytes, stream);
+  if (e == hipSuccess && stats) e = hipMemsetAsync(stats, 0, out[3].bytes, stream);
+  if (e == hipSuccess) {
+    const bool conn8 = connectivity == 8;
+    const dim3 tgrid((unsigned)tiles), cgrid((unsigned)chunks, (unsigned)n);
+    comp_tile_kernel<<<tgrid, COMP_THREADS, 0, stream>>>(code, n, w, h, ntx, (unsigned)fg_codes, conn8, par, aux);
+    const int nrow = (nty - 1) * w, total = nrow + (ntx - 1) * h;                   // < 2^25
+    if (total > 0)
+      comp_merge_kernel<<<dim3((unsigned)((total + COMP_THREADS - 1) / COMP_THREADS), (unsigned)n), COMP_THREADS, 0, stream>>>(
+          par, w, h, conn8, nrow, total);
+    comp_flatten_kernel<<<tgrid, COMP_THREADS, 0, stream>>>(par, aux, n, w, h, ntx);
+    comp_count_kernel<<<cgrid, COMP_THREADS, 0, stream>>>(par, aux, (int)hw, min_area, chunk_cnt, stats);
+    comp_scan_kernel<<<dim3((unsigned)n), COMP_THREADS, 0, stream>>>(chunk_cnt, chunks, max_objects, stats);
+    comp_emit_kernel<<<cgrid, COMP_THREADS, 0, stream>>>(par, aux, w, (int)hw, min_area, chunk_cnt, max_objects, objects);
+    if (values)
+      comp_reduce_kernel<true><<<tgrid, COMP_THREADS, 0, stream>>>(par, aux, values, n, w, h, ntx, max_objects, objects, ids);
+    else
+      comp_reduce_kernel<false><<<tgrid, COMP_THREADS, 0, stream>>>(par, aux, nullptr, n, w, h, ntx, max_objects, objects, ids);
+    e = hipGetLastError();
+  }
+  const hipError_t ef = hipFreeAsync(ws, stream);
+  if (e == hipSuccess) e = ef;
+  return e == hipSuccess ? FOTG_OK : hip_fail(e);
+}
+
+int fotg_components_tile(int *tw, int *th)
+{
+  if (tw) *tw = COMP_TW;
+  if (th) *th = COMP_TH;
+  return FOTG_OK;
+}
+
+}  // extern "C"

@@ -286,6 +286,14 @@ class OFClass:
         from .motion import ofc_stabilize
         return ofc_stabilize(self, frames, model=model, radius=radius, fill=fill, stats=stats, iters=iters, thresh=thresh)
 
+    def moving_objects(self, frames, model="affine", iters=3, thresh=1.0, min_area=64, max_objects=256, connectivity=8, ids=False,
+                       stats=False):
+        """the flows of frames (T+1, ...), the camera motion of each, and the pixels that do not follow it grouped into objects:
+        (params (T, 6), objects (T, max_objects, 11)[, ids][, stats]) -- flowonthego_amd.objects"""
+        from .objects import ofc_moving_objects
+        return ofc_moving_objects(self, frames, model=model, iters=iters, thresh=thresh, min_area=min_area, max_objects=max_objects,
+                                  connectivity=connectivity, ids=ids, stats=stats)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

@@ -508,6 +508,36 @@ int fotg_motion_flow(int device, int n, const double *params, int w, int h, floa
  * calls (any other value only queries) and returns the previous one. */
 int fotg_motion_ending(int ending);
 
+/* ---- objects: the connected components of a code map, with a record each, csrc/components.hip.h ---------------------------------
+ * What turns the per-pixel codes of the motion fit (1 = independent motion), the consistency check or the warp into a list of
+ * regions.  In order:
+ * Input: code n x h x w uint8, 1 <= w, h <= 16384; fg_codes, an 8-bit set with at least one bit: pixel p is foreground iff
+ * code[p] < 8 && ((fg_codes >> code[p]) & 1); connectivity 4 or 8 (links between horizontal and vertical neighbours, at 8 also
+ * diagonal ones); components never join across the images of the batch; values NULL or n x h x w x 2 f32 (the fit's residual).
+ * Label: the linear index y w + x of the component's first pixel in raster order = the minimum linear index over its pixels; it
+ * does not depend on tile shape, launch shape, arrival order or route.
+ * Record, eleven int64, each independent of the order of reduction: label, area, xmin, ymin, xmax, ymax, sum x, sum y, n_val,
+ * sum U, sum V, with U = (int)rintf(256 u), V = (int)rintf(256 v) of the pixel's vector in `values`, left out unless |u| <= 4096
+ * && |v| <= 4096 (false for a NaN or an infinity); n_val counts the admissible pixels; n_val = sum U = sum V = 0 without values.
+ * For w, h <= 16384 none can overflow: area <= 2^28, sum x, sum y < 2^28 x 2^14 = 2^42, |sum U|, |sum V| <= 2^28 x 2^20 = 2^48.
+ * Selection and order: a component is kept iff area >= min_area (>= 1); the kept ones in ascending label order are the rows of
+ * objects, n x max_objects x 11 (1 <= max_objects <= 65536): at most the first max_objects are written, every later row is zero.
+ * Outputs on the device, each but objects may be NULL:
+ *   labels  n x h x w int32: the component's label, -1 for background (components below min_area keep theirs)
+ *   ids     n x h x w int32: the row of the pixel's component in objects, -1 for background, a component too small or one beyond
+ *           max_objects
+ *   stats   n x 4 int64: foreground pixels, components, components with area >= min_area, rows written
+ * Integer atomics only: the same bytes every run.  Asynchronous on `stream`; the scratch (a parent and an area entry per pixel) is
+ * taken from and returned to the stream's memory pool.  FOTG_ERR_ARG, decided before the device is touched and before anything is
+ * launched or cleared: n < 1 (or > 65535, or more than 2^31 - 1 tiles of 64 x 16 in the batch), w or h < 1 or > 16384, fg_codes
+ * < 1 or > 255, a connectivity other than 4 and 8, min_area < 1, max_objects < 1 or > 65536, a null code or objects, an output
+ * overlapping an input or another output. */
+int fotg_label_components(int device, int n, const unsigned char *code, int w, int h, int fg_codes, int connectivity,
+                          const float *values, long long min_area, int max_objects, int *labels, int *ids, long long *objects,
+                          long long *stats, void *stream);
+/* the tile of the labelling kernels, in pixels (tests place structures on its edges and corners); either pointer may be NULL */
+int fotg_components_tile(int *tw, int *th);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
