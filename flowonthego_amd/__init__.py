@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ("warp", "upsample_crop_warp"):
         import importlib
         return getattr(importlib.import_module(".warp", __name__), name)
+    if name in ("temporal_filter", "upsample_crop_temporal_filter"):
+        import importlib
+        return getattr(importlib.import_module(".temporal", __name__), name)
     if name in ("chain", "track_points", "upsample_crop_chain", "upsample_crop_track_points"):
         import importlib
         return getattr(importlib.import_module(".chain", __name__), name)

@@ -90,6 +90,10 @@ SYMBOLS = [
     ("fotg_motion_ending", C.c_int, [C.c_int]),
     ("fotg_label_components", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, C.c_int, vp, vp, vp, vp, vp]),
     ("fotg_components_tile", C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("fotg_temporal_filter", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_temporal_filter_u8", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_temporal_filter", C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_temporal_filter_u8", C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]),
     ("fotg_level_size", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_out_size", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_num_patches", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

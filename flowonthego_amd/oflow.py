@@ -294,6 +294,20 @@ class OFClass:
         return ofc_moving_objects(self, frames, model=model, iters=iters, thresh=thresh, min_area=min_area, max_objects=max_objects,
                                   connectivity=connectivity, ids=ids, stats=stats)
 
+    def upsample_crop_temporal_filter(self, flows, frames, center, neighbors, masks=None, tau=30.0, gains=None, ref=None, stats=False,
+                                      fused=True):
+        """the centre frames filtered with their neighbours pulled onto them along upsample_crop(flows), flows (n K, h_l, w_l, 2)
+        of the pairs (centre, neighbour) -- flowonthego_amd.temporal"""
+        from .temporal import upsample_crop_temporal_filter
+        return upsample_crop_temporal_filter(self, flows, frames, center, neighbors, masks=masks, tau=tau, gains=gains, ref=ref,
+                                             stats=stats, fused=fused)
+
+    def temporal_filter(self, frames, radius=1, tau=30.0, gains=None, occlusion=False, ref=None, stats=False):
+        """every frame of the stack (T, ...) averaged with its neighbours at distance +-1 .. +-radius, each pulled onto it along
+        its own flow and weighted by the local photometric difference (temporal denoising) -- flowonthego_amd.temporal"""
+        from .temporal import ofc_temporal_filter
+        return ofc_temporal_filter(self, frames, radius=radius, tau=tau, gains=gains, occlusion=occlusion, ref=ref, stats=stats)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

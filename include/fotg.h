@@ -538,6 +538,60 @@ int fotg_label_components(int device, int n, const unsigned char *code, int w, i
 /* the tile of the labelling kernels, in pixels (tests place structures on its edges and corners); either pointer may be NULL */
 int fotg_components_tile(int *tw, int *th);
 
+/* ---- motion-compensated temporal filtering of a frame sequence (denoising, multi-frame fusion), csrc/temporal.hip.h ------------
+ * The frames around a centre frame are pulled onto it along their flows and averaged with it, each with a per-pixel weight that
+ * falls with the photometric difference in a 3 x 3 window.  All arithmetic f32, every operation rounded on its own, in this order.
+ * Inputs: frames, a stack of T frames w x h x channels, channels 1 or 3 interleaved, f32 (fotg_temporal_filter) or 8-bit
+ * (fotg_temporal_filter_u8; taps converted exactly to f32), on the device.  For each of the n output images a centre index c =
+ * center[i] and K neighbour indices b_1 .. b_K = neighbors[i K ..], 1 <= K <= 8; a neighbour index of -1 means absent and is
+ * skipped entirely.  For each neighbour a flow F_k (centre -> neighbour, full resolution; flows: n x K x h x w x 2 f32) and
+ * optionally a mask m_k in fotg_fb_check's alphabet (masks: NULL or n x K x h x w uint8).  tau > 0.  K gains g_k, finite and >= 0
+ * (gains NULL: all 1).  scale = 1.0f / (tau * (float)(9 * channels)), computed once on the host in f32.
+ * Per neighbour k, per pixel q of the centre C = frame c; taps, own and code are exactly fotg_warp's in its reference fill mode
+ * with fill 0, with src = frame b_k, flow = F_k, occ = m_k:
+ *   W_k[q][ch] = own != 3 ? taps(frame b_k, q + F_k[q])[ch] : 0
+ *   d_k[q]     = the sum over the channels, in order, starting from the first term, of fabsf(C[q][ch] - W_k[q][ch])
+ *   r_k[x,y]   = (d_k[cl(x-1),y] + d_k[x,y]) + d_k[cl(x+1),y]
+ *   e_k[x,y]   = (r_k[x,cl(y-1)] + r_k[x,y]) + r_k[x,cl(y+1)]       (cl clamps to the image: a 3 x 3 box with replicated edges,
+ *                                                                    summed separably)
+ *   wt         = g_k * (1.0f - e_k * scale)
+ *   use_k      = code_k[x,y] == 0 && wt > 0                           (a NaN fails this test)
+ * Per pixel, k in ascending order:
+ *   num[ch] = C[ch];  den = 1.0f;  used = 0
+ *   for each neighbour with use_k:  num[ch] = num[ch] + wt * W_k[ch];  den = den + wt;  used++
+ *   value[ch] = num[ch] / den                                         (a correctly rounded division; den >= 1)
+ * Outputs, each may be NULL (not all three): dst, n images of the frames' layout and type (an 8-bit dst is rounded as fotg_warp's;
+ * it must not overlap the frames); used: n x h x w uint8; stats: n x 4 f64 per image: [0] the sum of used over the image, [1] the
+ * number of pixels with used == 0 and, with a clean comparison stack ref (n images of dst's layout and type) over all pixels and
+ * channels [2] sum (double)|ref - value| and [3] sum (double)|ref - C|, each term the f32 fabsf of the f32 difference of the
+ * unrounded value; without ref both are 0.  The sums are added in a fixed order (no floating-point atomics): the same bits every
+ * run, and the same from the dense and the fused form.
+ * center (n ints), neighbors (n x K ints) and gains (K floats) are HOST arrays: validated on the host and consumed before the call
+ * returns; the indices reach the kernel by a stream-ordered copy into memory of the call, the gains by value.  Everything else is
+ * enqueued on `stream`; the partial sums live in stream-ordered memory of the call.
+ * FOTG_ERR_ARG, decided before anything is launched: n < 1 (or > 65535), K outside 1..8, T < 1, w or h <= 0, channels not 1 or 3,
+ * tau not finite or <= 0, a gain negative or not finite, a centre index outside [0, T), a neighbour index outside [-1, T), a null
+ * frames, flows, center or neighbors, all three outputs null, dst overlapping the frames. */
+int fotg_temporal_filter(int device, int n, int K, int T, const float *frames, int w, int h, int channels, const int *center,
+                         const int *neighbors, const float *flows, const unsigned char *masks, float tau, const float *gains,
+                         const float *ref, float *dst, unsigned char *used, double *stats, void *stream);
+int fotg_temporal_filter_u8(int device, int n, int K, int T, const unsigned char *frames, int w, int h, int channels,
+                            const int *center, const int *neighbors, const float *flows, const unsigned char *masks, float tau,
+                            const float *gains, const unsigned char *ref, unsigned char *dst, unsigned char *used, double *stats,
+                            void *stream);
+/* The same along the coarse flows of a context (n K x hl x wl x 2, in the order a batch fotg_calc_batch of the pairs (centre,
+ * neighbour) returns them: image-major, neighbour-minor), upsampled and cropped on the fly, frames of h_org x w_org: every output
+ * equals fotg_temporal_filter on fotg_upsample_crop's output byte for byte, the statistics included, without writing a
+ * full-resolution flow.  FOTG_ERR_ARG also for n K > max_batch and a depth-mode context. */
+int fotg_upsample_crop_temporal_filter(fotg_ctx *ctx, int n, int K, int T, const float *coarse_flows, const float *frames,
+                                       int channels, const int *center, const int *neighbors, const unsigned char *masks, float tau,
+                                       const float *gains, const float *ref, float *dst, unsigned char *used, double *stats,
+                                       void *stream);
+int fotg_upsample_crop_temporal_filter_u8(fotg_ctx *ctx, int n, int K, int T, const float *coarse_flows,
+                                          const unsigned char *frames, int channels, const int *center, const int *neighbors,
+                                          const unsigned char *masks, float tau, const float *gains, const unsigned char *ref,
+                                          unsigned char *dst, unsigned char *used, double *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,

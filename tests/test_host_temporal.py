@@ -1,0 +1,106 @@
+"""The temporal filter's host side (no GPU needed): the C-ABI is declared and bound, examples/temporal_filter.cpp compiles and links
+against the C++ shim, the CLI refuses bad arguments, and the compiler's resource table lists every temporal_kernel instantiation
+without a private-memory segment.  With a GPU: the CLI writes what OFClass.temporal_filter returns and prints its numbers."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+NEW_SYMBOLS = ("fotg_temporal_filter", "fotg_temporal_filter_u8", "fotg_upsample_crop_temporal_filter",
+               "fotg_upsample_crop_temporal_filter_u8")
+
+
+def test_entry_points_are_declared_bound_and_exported():
+    import flowonthego_amd as F
+    from flowonthego_amd._lib import SYMBOLS
+    L = F.lib()
+    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
+    bound = {s[0]: s for s in SYMBOLS}
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\bint %s\(" % name, hdr), name
+        assert name in bound and hasattr(L, name)
+    # one ctypes argument per parameter of the declaration
+    for name in NEW_SYMBOLS:
+        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
+        assert len(decl.split(",")) == len(bound[name][2]), name
+    shim = open(os.path.join(ROOT, "include", "fotg", "temporal.h")).read()
+    for name in NEW_SYMBOLS:
+        assert name + "(" in shim
+    assert callable(F.temporal_filter) and callable(F.upsample_crop_temporal_filter)
+    from flowonthego_amd.oflow import OFClass
+    import flowonthego_amd.temporal as TM
+    assert callable(OFClass.temporal_filter) and callable(TM) and F.temporal_filter is TM.temporal_filter
+
+
+def test_neighbor_table():
+    from flowonthego_amd.temporal import neighbor_table
+    cen, nbr = neighbor_table(4, 2)
+    assert cen == [0, 1, 2, 3]
+    assert nbr == [[-1, 1, -1, 2], [0, 2, -1, 3], [1, 3, 0, -1], [2, -1, 1, -1]]
+    assert neighbor_table(1, 1) == ([0], [[-1, -1]])
+
+
+def test_temporal_filter_example_builds(tmp_path):
+    import flowonthego_amd as F
+    F.lib()
+    from test_host import _build_example
+    assert os.path.exists(_build_example(tmp_path, "temporal_filter"))
+
+
+def test_cli_argument_errors(tmp_path):
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for args in ([], ["a.npy"], ["a.npy", "b.npy", "c.npy"], ["a.npy", "b.npy", "--radius", "x"], ["a.npy", "b.npy", "--radius", "0"],
+                 ["a.npy", "b.npy", "--radius", "5"], ["a.npy", "b.npy", "--tau", "0"], ["a.npy", "b.npy", "--tau"],
+                 ["a.npy", "b.npy", "--ref"], ["a.npy", "b.npy", "--nosuch"]):
+        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.denoise"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
+        assert r.returncode != 0 and "usage" in r.stderr, args
+
+
+def test_resource_table_lists_the_temporal_kernels_without_scratch():
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
+    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
+    names = re.findall(r"Function Name: (\S+)", txt)
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
+    assert len(names) == len(scratch)
+    table = dict(zip(names, scratch))
+    # Src x element type x channels, Itanium-mangled: temporal_kernel<DenseSrc | UpsampleSrc, float | unsigned char, 1 | 3>
+    for src in ("NS_8DenseSrcE", "NS_11UpsampleSrcE"):
+        for t in ("f", "h"):
+            for noc in (1, 3):
+                hit = [n for n in names if "temporal_kernelI%s%sLi%dE" % (src, t, noc) in n]
+                assert len(hit) == 1, (src, t, noc)
+                assert table[hit[0]] == 0, hit
+    fold = [n for n in names if "temporal_fold_kernel" in n]
+    assert len(fold) == 1 and table[fold[0]] == 0
+
+
+@pytest.mark.gpu
+def test_cli_writes_what_the_call_returns(tmp_path):
+    import torch
+    import flowonthego_amd as F
+    from flowonthego_amd.oflow import OFClass
+    rng = np.random.default_rng(4)
+    ys, xs = np.mgrid[0:48, 0:64]
+    clean = np.stack([128 + 60 * np.sin((ys + k) / 6.0) + 50 * np.cos((xs - 2 * k) / 5.0) for k in range(4)])
+    noisy = np.clip(np.rint(clean + rng.normal(0, 8, clean.shape)), 0, 255).astype(np.uint8)
+    clean = np.rint(clean).astype(np.uint8)
+    a, b, c = (str(tmp_path / n) for n in ("noisy.npy", "out.npy", "clean.npy"))
+    np.save(a, noisy)
+    np.save(c, clean)
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.denoise", a, b, "--radius", "1", "--tau", "25", "--ref", c],
+                       capture_output=True, text=True, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr
+    o = OFClass(F.operating_point(2, 64, 1), F.img_params(width=64, height=48), max_batch=8)
+    dst, used, st = o.temporal_filter(torch.from_numpy(noisy).cuda(), radius=1, tau=25.0, ref=torch.from_numpy(clean).cuda(), stats=True)
+    out = np.load(b)
+    assert out.dtype == np.uint8 and np.array_equal(out, dst.cpu().numpy())
+    got = [float(t) for t in re.findall(r"(-?\d+\.\d+)", r.stdout)]
+    psnr = lambda x: 10 * np.log10(255.0 ** 2 / np.mean((x.astype(np.float64) - clean) ** 2))
+    want = [psnr(noisy), psnr(out), float(used.float().mean())]
+    assert np.allclose(got, want, atol=1e-2), (r.stdout, want)
