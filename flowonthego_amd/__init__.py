@@ -24,6 +24,13 @@ def __getattr__(name):
     if name in ("temporal_filter", "upsample_crop_temporal_filter"):
         import importlib
         return getattr(importlib.import_module(".temporal", __name__), name)
+    if name in ("upsample_crop_filter_flow", "spatial_table"):
+        from . import flowfilter
+        return getattr(flowfilter, name)
+    if name == "filter_flow":
+        # (the command-line module of this name; it is callable as flowonthego_amd.flowfilter.filter_flow)
+        import importlib
+        return importlib.import_module(".filter_flow", __name__)
     if name in ("chain", "track_points", "upsample_crop_chain", "upsample_crop_track_points"):
         import importlib
         return getattr(importlib.import_module(".chain", __name__), name)

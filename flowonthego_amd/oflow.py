@@ -308,6 +308,23 @@ class OFClass:
         from .temporal import ofc_temporal_filter
         return ofc_temporal_filter(self, frames, radius=radius, tau=tau, gains=gains, occlusion=occlusion, ref=ref, stats=stats)
 
+    def upsample_crop_filter_flow(self, flow, guide, mask=None, radius=3, sigma=None, spatial=None, tau=20.0, iters=1, code=None,
+                                  stats=False, fused=True):
+        """upsample_crop(flow) filtered edge- and occlusion-aware with guide (n, h_org, w_org[, c]) and mask, fused: the unfiltered
+        full-resolution flow is never written -- flowonthego_amd.flowfilter"""
+        from .flowfilter import upsample_crop_filter_flow
+        return upsample_crop_filter_flow(self, flow, guide, mask=mask, radius=radius, sigma=sigma, spatial=spatial, tau=tau,
+                                         iters=iters, code=code, stats=stats, fused=fused)
+
+    def calc_filtered(self, I0, I1, radius=3, sigma=None, spatial=None, tau=20.0, iters=1, occlusion=True, both=False, code=None,
+                      stats=False):
+        """the full-resolution flow of n pairs, filtered with I0 as guide; occlusion=True (a bidir context) leaves the vectors the
+        forward-backward check rejects out and fills them from their neighbours; both=True also returns the backward flow
+        filtered with I1 -- flowonthego_amd.flowfilter"""
+        from .flowfilter import ofc_calc_filtered
+        return ofc_calc_filtered(self, I0, I1, radius=radius, sigma=sigma, spatial=spatial, tau=tau, iters=iters,
+                                 occlusion=occlusion, both=both, code=code, stats=stats)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

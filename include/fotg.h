@@ -592,6 +592,58 @@ int fotg_upsample_crop_temporal_filter_u8(fotg_ctx *ctx, int n, int K, int T, co
                                           const unsigned char *masks, float tau, const float *gains, const unsigned char *ref,
                                           unsigned char *dst, unsigned char *used, double *stats, void *stream);
 
+/* ---- edge- and occlusion-aware filtering of a flow, guided by the frame it belongs to, csrc/flowfilter.hip.h --------------------
+ * A joint (cross) bilateral filter of the vectors: a vector becomes the mean of the vectors of nearby pixels of similar colour,
+ * which pulls motion boundaries onto image edges; vectors a consistency mask rejects stay out of the mean, and a rejected pixel is
+ * filled from the consistent vectors around it.  All arithmetic f32, every operation rounded on its own, in this order.
+ * Inputs, per image of w x h: the flow F (flow: n x h x w x 2 f32); a guide G (guide: n x h x w x channels, channels 1 or 3
+ * interleaved, f32 (fotg_flow_filter) or 8-bit (fotg_flow_filter_u8; converted exactly to f32)); optionally a mask M (mask: NULL
+ * or n x h x w uint8, a mask of fotg_fb_check); a radius R, 1 <= R <= 7; spatial, R + 1 floats s[0 .. R], each finite and in
+ * [0, 1], s[0] > 0 (NULL: all 1); tau > 0; iters, 1 <= iters <= 4.  scale = 1.0f / (tau * (float)channels), computed once on the
+ * host in f32.
+ *   valid(q) = q is inside the image && both components of F(q) are finite && (no mask || M(q) == 0)
+ * One pass, pixel p:
+ *   nu = nv = den = 0
+ *   for dy = -R .. R ascending, inside it dx = -R .. R ascending, q = p + (dx, dy); a q outside the image is skipped (not
+ *   replicated):
+ *     d   = the sum over the channels, in order, starting from the first term, of fabsf(G(p)[ch] - G(q)[ch])
+ *     wt  = (s[|dy|] * s[|dx|]) * (1.0f - d * scale)
+ *     use = valid(q) && wt > 0                                            (a NaN fails this test)
+ *     if use:  nu = nu + wt * F(q).u;  nv = nv + wt * F(q).v;  den = den + wt     (an unused q contributes nothing)
+ *   if den > 0:  out = (nu / den, nv / den)  (correctly rounded divisions);  code = valid(p) ? 0 : 1   (1: filled from neighbours)
+ *   otherwise:   out = F(p) bit for bit;  code = 3                                                     (3: no support)
+ * A valid centre with a finite guide pixel supports itself (d = 0, wt = s[0]^2 > 0) and gets code 0.
+ * Several passes: pass k >= 2 is pass 1 applied to the output of pass k - 1 with the mask (code of pass k - 1 == 3) and the same
+ * guide.  The final code is 3 where the last pass says 3, otherwise 0 where pass 1 said 0, otherwise 1; the final vectors are the
+ * last pass's.  iters = k equals k calls with iters = 1 composed that way, bit for bit.
+ * Outputs, each may be NULL (not all three): out, n x h x w x 2 f32 (it must not overlap the flow; with iters > 1 it also holds
+ * intermediate passes before the final one); code, n x h x w uint8; stats, n x 4 f64 per image: the pixels of final code [0] 0,
+ * [1] 1 and [2] 3, and [3] over the pixels of final code 0 the sum of (double)fabsf(out.u - F.u) and (double)fabsf(out.v - F.v),
+ * F the input of pass 1, each term the f32 fabsf of the f32 difference, terms that are not finite left out.  The sums are added
+ * in a fixed order (no floating-point atomics): the same bits every run, and the same from the dense and the fused form.
+ * spatial is a HOST array, validated on the host, consumed before the call returns and passed to the kernel by value.
+ * Everything else is enqueued on `stream`; the vectors and codes between passes and the partial sums live in stream-ordered
+ * memory of the call.
+ * FOTG_ERR_ARG, decided before anything is launched: n < 1 (or > 65535), w or h <= 0, channels not 1 or 3, radius outside 1..7,
+ * iters outside 1..4, tau not finite or <= 0, a spatial entry not finite or outside [0, 1], s[0] == 0, a null flow or guide, all
+ * three outputs null, out overlapping the flow. */
+int fotg_flow_filter(int device, int n, const float *flow, const float *guide, int w, int h, int channels, const unsigned char *mask,
+                     int radius, const float *spatial, float tau, int iters, float *out, unsigned char *code, double *stats,
+                     void *stream);
+int fotg_flow_filter_u8(int device, int n, const float *flow, const unsigned char *guide, int w, int h, int channels,
+                        const unsigned char *mask, int radius, const float *spatial, float tau, int iters, float *out,
+                        unsigned char *code, double *stats, void *stream);
+/* The same on the coarse flow of a context (n x hl x wl x 2, as fotg_calc_batch returns it), upsampled and cropped on the fly,
+ * guide and mask of h_org x w_org: every output equals fotg_flow_filter on fotg_upsample_crop's output bit for bit, the
+ * statistics included, without the unfiltered full-resolution flow ever being written.  FOTG_ERR_ARG also for n > max_batch, a
+ * depth-mode context and out overlapping the coarse flow. */
+int fotg_upsample_crop_flow_filter(fotg_ctx *ctx, int n, const float *coarse_flow, const float *guide, int channels,
+                                   const unsigned char *mask, int radius, const float *spatial, float tau, int iters, float *out,
+                                   unsigned char *code, double *stats, void *stream);
+int fotg_upsample_crop_flow_filter_u8(fotg_ctx *ctx, int n, const float *coarse_flow, const unsigned char *guide, int channels,
+                                      const unsigned char *mask, int radius, const float *spatial, float tau, int iters, float *out,
+                                      unsigned char *code, double *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
