@@ -31,6 +31,13 @@ def __getattr__(name):
         # (the command-line module of this name; it is callable as flowonthego_amd.flowfilter.filter_flow)
         import importlib
         return importlib.import_module(".filter_flow", __name__)
+    if name == "upsample_crop_block_motion":
+        from . import blockmotion
+        return blockmotion.upsample_crop_block_motion
+    if name == "block_motion":
+        # (the command-line module of this name; it is callable as flowonthego_amd.blockmotion.block_motion)
+        import importlib
+        return importlib.import_module(".block_motion", __name__)
     if name in ("chain", "track_points", "upsample_crop_chain", "upsample_crop_track_points"):
         import importlib
         return getattr(importlib.import_module(".chain", __name__), name)

@@ -325,6 +325,20 @@ class OFClass:
         return ofc_calc_filtered(self, I0, I1, radius=radius, sigma=sigma, spatial=spatial, tau=tau, iters=iters,
                                  occlusion=occlusion, both=both, code=code, stats=stats)
 
+    def upsample_crop_block_motion(self, flow, cur, ref, mask=None, block=16, refine=2, pred=False, stats=False, fused=True):
+        """one quarter-pel motion vector per block x block pixels of cur, predicting it from ref, chosen among the vectors
+        upsample_crop(flow) proposes, with its SAD; fused: the full-resolution flow is never written -- flowonthego_amd.blockmotion"""
+        from .blockmotion import upsample_crop_block_motion
+        return upsample_crop_block_motion(self, flow, cur, ref, mask=mask, block=block, refine=refine, pred=pred, stats=stats,
+                                          fused=fused)
+
+    def block_motion(self, I0, I1, block=16, refine=2, occlusion=False, pred=False, stats=False):
+        """the flow of n 8-bit frame pairs and the block motion vectors that predict I0 from I1, in one call: (flow, mv, cost,
+        kind[, pred][, stats]); occlusion=True (a bidir context) keeps the vectors the forward-backward check rejects from
+        proposing candidates -- flowonthego_amd.blockmotion"""
+        from .blockmotion import ofc_block_motion
+        return ofc_block_motion(self, I0, I1, block=block, refine=refine, occlusion=occlusion, pred=pred, stats=stats)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

@@ -644,6 +644,53 @@ int fotg_upsample_crop_flow_filter_u8(fotg_ctx *ctx, int n, const float *coarse_
                                       const unsigned char *mask, int radius, const float *spatial, float tau, int iters, float *out,
                                       unsigned char *code, double *stats, void *stream);
 
+/* ---- block motion vectors from a dense flow, for a video encoder, csrc/blockmotion.hip.h ------------------------------------------
+ * One quarter-pel vector per B x B block, chosen among the vectors the flow proposes for the block because it makes the
+ * motion-compensated prediction cheap, with its SAD.  Integer arithmetic from the first step to the last: the same bytes in any
+ * reduction order.
+ * Inputs: cur, ref, 8-bit frames n x h x w x channels (channels 1 or 3, interleaved); flow, n x h x w x 2 f32 from cur to ref, so
+ * that cur(x) ~ ref(x + flow(x)); mask, NULL or n x h x w uint8 in the alphabet of fotg_fb_check (only a byte equal to 0 is valid;
+ * bytes above 3 are invalid like 1 .. 3); block B in {8, 16, 32}; refine in {0, 1, 2, 3}; 1 <= w, h <= 16384.
+ * Per pixel:
+ *   known = |u| <= 4096 && |v| <= 4096                                    (false for a NaN or an infinity)
+ *   Qx = (int)rintf(u * 4), Qy alike, in quarter pixels                   (the product is exact, to nearest even, |Q| <= 16384)
+ *   admissible = known && (no mask || mask == 0)
+ * Block grid: bw = ceil(w / B), bh = ceil(h / B); block (bx, by) covers x in [bx B, min(bx B + B, w)) and y alike.  Pixels beyond the
+ * frame do not exist: they add nothing to any sum.
+ * Prediction of pixel (x, y), channel k, by the vector (mx, my), all integers:
+ *   ix = 4 x + mx;  X0 = ix >> 2 (arithmetic shift: floor);  fx = ix & 3;  iy, Y0, fy alike
+ *   the taps a, b, c, d are ref at (X0, Y0), (X0 + 1, Y0), (X0, Y0 + 1), (X0 + 1, Y0 + 1), every tap coordinate clamped on its own
+ *   to [0, w - 1] or [0, h - 1] (the encoder's edge padding)
+ *   pred = ((4 - fx)(4 - fy) a + fx (4 - fy) b + (4 - fx) fy c + fx fy d + 8) >> 4
+ * SAD(m) = the sum of |cur - pred| over the block's pixels and channels.
+ * Candidates, in this order (one with nothing to compute from is absent):
+ *   0       the zero vector, always present
+ *   1       the block mean: with S = the sum of Q over the block's admissible pixels and m their count, floor((2 S + m) / (2 m)) per
+ *           component (a floor division); absent when m = 0
+ *   2       Q of the pixel (min(bx B + B/2, w - 1), min(by B + B/2, h - 1)), if that pixel is admissible
+ *   3 .. 6  the means, by the same rule, of the four B/2 x B/2 quadrants clipped to the frame, top-left, top-right, bottom-left,
+ *           bottom-right, each a candidate for the whole block
+ * The winner is the lowest SAD; ties go to the lowest index.
+ * Refinement: the steps are the last `refine` entries of (4, 2, 1).  Per step s the eight vectors m + s (dx, dy) are evaluated, (dx,
+ * dy) in the order (-1,-1), (0,-1), (1,-1), (-1,0), (1,0), (-1,1), (0,1), (1,1), skipping any with a component beyond +-16384; the
+ * vector moves to the lowest SAD only if it is strictly lower than the current one, the earliest in that order among equals.
+ * Outputs per block: mv, n x bh x bw x 2 int16, in quarter pixels; cost, n x bh x bw x 2 uint32 = [SAD of the final vector, SAD of
+ * the zero vector]; kind, n x bh x bw uint8 = the winning candidate | (8 if a refinement step moved the vector).  Optional (NULL:
+ * left out): pred, uint8 shaped like cur, the prediction by each block's final vector (it must not overlap cur or ref); stats, n x
+ * 11 int64 per image = [0] sum of SAD, [1] sum of the zero-vector SAD, [2] sum of (cur - pred)^2, [3] the blocks moved, [4 .. 10]
+ * the blocks per winning candidate 0 .. 6.  Two identical calls give identical bytes.  Everything is enqueued on `stream`.
+ * FOTG_ERR_ARG, decided before anything is launched: n < 1 (or > 65535), w or h outside 1 .. 16384, channels not 1 or 3, block not
+ * 8, 16 or 32, refine outside 0 .. 3, a null cur, ref, flow, mv, cost or kind, pred overlapping cur or ref. */
+int fotg_block_motion(int device, int n, const unsigned char *cur, const unsigned char *ref, int w, int h, int channels,
+                      const float *flow, const unsigned char *mask, int block, int refine, short *mv, unsigned *cost,
+                      unsigned char *kind, unsigned char *pred, long long *stats, void *stream);
+/* The same on the coarse flow of a context (n x hl x wl x 2, as fotg_calc_batch returns it), upsampled and cropped on the fly, frames
+ * and mask of h_org x w_org: every output equals fotg_block_motion on fotg_upsample_crop's output bit for bit, without the
+ * full-resolution flow ever being written.  FOTG_ERR_ARG also for n > max_batch and a depth-mode context. */
+int fotg_upsample_crop_block_motion(fotg_ctx *ctx, int n, const float *coarse_flow, const unsigned char *cur, const unsigned char *ref,
+                                    int channels, const unsigned char *mask, int block, int refine, short *mv, unsigned *cost,
+                                    unsigned char *kind, unsigned char *pred, long long *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
