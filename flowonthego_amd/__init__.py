@@ -47,8 +47,11 @@ def __getattr__(name):
     if name in ("label_components", "object_summary", "OBJECT", "OBJECT_STATS"):
         from . import objects
         return getattr(objects, name)
-    if name in ("fit_motion", "stabilize", "moving_objects"):
-        # (the command-line modules of these names; each is callable as the function of flowonthego_amd.motion)
+    if name in ("object_overlap", "upsample_crop_object_overlap", "object_links", "link_tracks", "TRACK", "TRACK_STATS"):
+        from . import tracks
+        return getattr(tracks, name)
+    if name in ("fit_motion", "stabilize", "moving_objects", "track_objects"):
+        # (the command-line modules of these names; each is callable as the function of flowonthego_amd.motion / objects / tracks)
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("interpolate", "upsample_crop_interpolate"):

@@ -339,6 +339,22 @@ class OFClass:
         from .blockmotion import ofc_block_motion
         return ofc_block_motion(self, I0, I1, block=block, refine=refine, occlusion=occlusion, pred=pred, stats=stats)
 
+    def upsample_crop_object_overlap(self, flow, ids_a, ids_b, mask=None, ka=256, kb=256, fused=True):
+        """the overlap votes between the objects of two frames along upsample_crop(flow): (votes (n, ka, kb), sent (n, ka, 4)); fused:
+        the full-resolution flow is never written -- flowonthego_amd.tracks"""
+        from .tracks import upsample_crop_object_overlap
+        return upsample_crop_object_overlap(self, flow, ids_a, ids_b, mask=mask, ka=ka, kb=kb, fused=fused)
+
+    def track_objects(self, frames, model="affine", iters=3, thresh=1.0, min_area=64, max_objects=256, connectivity=8, min_votes=16,
+                      min_frac=0.25, max_tracks=1024, track_ids=False, stats=False):
+        """the moving objects of frames (T+1, ...) as moving_objects finds them, linked across frames by the flow into tracks:
+        (params (T, 6), objects (T, max_objects, 11), track (T, max_objects), tracks (max_tracks, 8)[, track_ids][, stats]) --
+        flowonthego_amd.tracks"""
+        from .tracks import ofc_track_objects
+        return ofc_track_objects(self, frames, model=model, iters=iters, thresh=thresh, min_area=min_area, max_objects=max_objects,
+                                 connectivity=connectivity, min_votes=min_votes, min_frac=min_frac, max_tracks=max_tracks,
+                                 track_ids=track_ids, stats=stats)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

@@ -1,0 +1,91 @@
+"""python -m flowonthego_amd.track_objects frames.npy out.npz [--model translation|similarity|affine] [--iters N] [--thresh PX]
+                                            [--min-area N] [--max-objects N] [--min-votes N] [--min-frac F] [--max-tracks N]
+                                            [--op-point K] [--ids out.npy]
+
+Tracks the moving objects of a video on the GPU: frames.npy holds a (T+1, h, w) or (T+1, h, w, 3) uint8 or float32 array, T >= 2.
+The flows of the sequence are computed (both directions, so that occluded pixels neither fit nor vote), the camera motion is fitted
+to each, the pixels that do not follow it are grouped into objects and the objects of consecutive frames are linked by the flow
+(OFClass.track_objects).  out.npz gets params (T, 6), objects (T, max_objects, 11), track (T, max_objects), tracks (max_tracks, 8)
+and stats (4); --ids: the track id of every pixel, int32 (T, h, w), -1 for background.  Prints one line per track:
+id  frames first .. last  rows first last  mean area  largest area  votes  how it ended.
+
+The module is callable: flowonthego_amd.track_objects(ids, objects, flows, ...) is flowonthego_amd.tracks.track_objects(...)."""
+import argparse
+import sys
+import types
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="track_objects", description=__doc__.splitlines()[0])
+    ap.add_argument("frames")
+    ap.add_argument("out")
+    ap.add_argument("--model", default="affine")
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--thresh", type=float, default=1.0)
+    ap.add_argument("--min-area", type=int, default=64)
+    ap.add_argument("--max-objects", type=int, default=256)
+    ap.add_argument("--min-votes", type=int, default=16)
+    ap.add_argument("--min-frac", type=float, default=0.25)
+    ap.add_argument("--max-tracks", type=int, default=1024)
+    ap.add_argument("--op-point", type=int, default=2)
+    ap.add_argument("--ids", default=None)
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if a.iters < 0 or a.iters > 64 or not a.thresh >= 0:
+        ap.error("--iters must be in 0 .. 64 and --thresh >= 0")
+    if a.min_area < 1 or a.max_objects < 1 or a.max_objects > 1024:
+        ap.error("--min-area must be >= 1 and --max-objects in 1 .. 1024")
+    if a.min_votes < 1 or not 0 <= a.min_frac <= 1 or a.max_tracks < 1 or a.max_tracks > 65536:
+        ap.error("--min-votes must be >= 1, --min-frac in 0 .. 1 and --max-tracks in 1 .. 65536")
+    from .motion import MODELS                           # (imports torch: after the checks that do not need it)
+    if a.model not in MODELS:
+        ap.error("--model must be one of " + ", ".join(MODELS))
+    import numpy as np
+    import torch
+    from . import img_params, operating_point
+    from .oflow import OFClass
+    from .tracks import ENDS
+    try:
+        frames = np.load(a.frames)
+    except (OSError, ValueError) as e:
+        sys.stderr.write("track_objects: %s\n" % e)
+        return 1
+    if frames.ndim not in (3, 4) or frames.shape[0] < 3 or frames.dtype not in (np.uint8, np.float32) or (frames.ndim == 4 and frames.shape[3] not in (1, 3)):
+        sys.stderr.write("track_objects: %s must hold a (T+1, h, w) or (T+1, h, w, 3) uint8 or float32 array, T >= 2\n" % a.frames)
+        return 1
+    if frames.ndim == 4 and frames.shape[3] == 1:
+        frames = frames[..., 0]
+    T, h, w = frames.shape[0] - 1, frames.shape[1], frames.shape[2]
+    color = frames.ndim == 4
+    u8_rgb = color and frames.dtype == np.uint8          # 8-bit colour frames become gray on load; float32 ones are used as RGB
+    op = operating_point(a.op_point, w, 3 if color and not u8_rgb else 1)
+    op.bidir = True
+    if u8_rgb:
+        op.u8_color = 2
+    ofc = OFClass(op, img_params(width=w, height=h), max_batch=T)
+    params, objects, track, tracks, ids, st = ofc.track_objects(
+        torch.from_numpy(np.ascontiguousarray(frames)).cuda(), model=a.model, iters=a.iters, thresh=a.thresh, min_area=a.min_area,
+        max_objects=a.max_objects, min_votes=a.min_votes, min_frac=a.min_frac, max_tracks=a.max_tracks, track_ids=True, stats=True)
+    st, table = st.cpu().numpy(), tracks.cpu().numpy()
+    np.savez(a.out, params=params.cpu().numpy(), objects=objects.cpu().numpy(), track=track.cpu().numpy(), tracks=table, stats=st)
+    if a.ids:
+        np.save(a.ids, ids.cpu().numpy())
+    for k, r in enumerate(table[:int(st[1])]):
+        print("%d  frames %d .. %d  rows %d %d  mean area %.1f  largest %d  votes %d  %s" % (k, r[0], r[1], r[2], r[3], r[4] / (r[1] - r[0] + 1), r[5],
+                                                                                           r[6], ENDS[int(r[7])]))
+    print("%d tracks over %d object maps (%d links, %d alive at the end)%s" % (st[0], T, st[2], st[3],
+                                                                              "" if st[0] == st[1] else ", the first %d listed" % st[1]))
+    ofc.close()
+    return 0
+
+
+class _Callable(types.ModuleType):
+    """importing this submodule binds the package attribute `track_objects` to the module: calling it calls tracks.track_objects()"""
+    def __call__(self, *a, **kw):
+        from .tracks import track_objects
+        return track_objects(*a, **kw)
+
+
+sys.modules[__name__].__class__ = _Callable
+
+if __name__ == "__main__":
+    sys.exit(main())

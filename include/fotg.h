@@ -691,6 +691,57 @@ int fotg_upsample_crop_block_motion(fotg_ctx *ctx, int n, const float *coarse_fl
                                     int channels, const unsigned char *mask, int block, int refine, short *mv, unsigned *cost,
                                     unsigned char *kind, unsigned char *pred, long long *stats, void *stream);
 
+/* ---- object tracks: the objects of fotg_label_components linked across frames by the flow, csrc/objtracks.hip.h -----------------
+ * What gives the per-frame objects an identity that persists over time, and says when an object enters, leaves, merges or splits.
+ * Integer arithmetic from the first step to the last: the same bytes in any order of reduction.  Three steps, three calls.
+ * Step 1, overlap votes, per pair of frames a -> b (fotg_object_overlap).  Inputs: ids_a, ids_b, int32 n x h x w, the `ids` of
+ * fotg_label_components (the row of the pixel's object, -1 for none); flow, n x h x w x 2 f32, a -> b on a's grid; mask, NULL or
+ * n x h x w uint8 in the alphabet of fotg_fb_check (only a byte equal to 0 votes); the row counts ka, kb in 1 .. 1024; 1 <= w, h <=
+ * 16384.  For every pixel (x, y) with i = ids_a in [0, ka), in this order (any other value of ids_a, negative or >= ka, is background
+ * and is ignored):
+ *   1. the pixel is inadmissible if the mask is non-zero, u or v is not finite, |u| > 4096 or |v| > 4096:  sent[i][3]++
+ *   2. otherwise xq = x + (int)rintf(u), yq = y + (int)rintf(v) (round half to even); the target outside the frame:  sent[i][2]++
+ *   3. otherwise j = ids_b[yq][xq]:  j in [0, kb): votes[i][j]++ and sent[i][0]++;  otherwise (background): sent[i][1]++
+ * Outputs: votes, int32 n x ka x kb; sent, int64 n x ka x 4; both cleared by the call.  The four columns of sent[i] add up to the
+ * number of pixels carrying id i.  Pairs of a batch never mix.  For a sequence of T + 1 id maps the caller passes ids and ids + h w
+ * with n = T.
+ * Step 2, links (fotg_object_links).  Inputs: votes; the two object tables objects_a, objects_b (int64 n x ka x 11 and n x kb x 11 as
+ * fotg_label_components writes them; the area is column 1); min_votes >= 1; min_frac256 in 0 .. 256.
+ *   best_b(i) = the lowest j that maximises votes[i][.], defined only if that maximum is > 0
+ *   best_a(j) = the lowest i that maximises votes[.][j], likewise
+ *   i and j are matched iff best_b(i) = j, best_a(j) = i, votes[i][j] >= min_votes and
+ *   256 votes[i][j] >= min_frac256 min(area_a[i], area_b[j]), evaluated in 64-bit integers
+ * Outputs: link_ab, int32 n x ka x 3 = (the matched j or -1, best_b(i) or -1, the votes of that best or 0); link_ba, int32 n x kb x 3
+ * likewise.  A match is one-to-one by construction.
+ * Step 3, tracks over one sequence; time is the batch axis (fotg_object_tracks).  T + 1 frames, T pairs, K rows per frame: objects
+ * (T + 1) x K x 11, link_ab and link_ba T x K x 3.  A row counts as written iff its area > 0.
+ *   frame 0: the written rows get the track ids 0, 1, .. in row order
+ *   frame t + 1, rows in ascending order: a written row j whose link_ba[t][j] names a match i (in [0, K)) inherits track[t][i]; any
+ *   other written row gets the next unused id;  unwritten rows get -1
+ * Outputs: track, int32 (T + 1) x K; tracks, int64 max_tracks x 8, one row per track id < max_tracks, the others zero: first_frame,
+ * last_frame, first_row, last_row, the sum of its areas, the largest area, the sum of the votes over its links, end; stats (may be
+ * NULL), int64 x 4 = tracks started, tracks with a table row, links made, tracks alive at frame T.  A track has exactly one object
+ * per frame from first_frame to last_frame.  end, read at the track's last frame t from its row i:
+ *   0  alive at frame T
+ *   1  its best target is mutual (best_a(best_b(i)) = i) but a threshold failed
+ *   2  its best target prefers another object (a merge, or a tie lost to a lower row)
+ *   3  link_ab[t][i] has no best target: no pixel of it landed on an object (it left the frame or vanished)
+ * All ties are decided by the lower index.  Two identical calls give identical bytes; there are no floating-point atomics.
+ * Everything is enqueued on `stream`.  FOTG_ERR_ARG, decided before anything is launched or cleared: n or T < 1 (or > 65535), w or h
+ * outside 1 .. 16384, ka, kb or K outside 1 .. 1024, min_votes < 1, min_frac256 outside 0 .. 256, max_tracks outside 1 .. 65536, a
+ * null pointer other than mask and stats, an output overlapping an input or another output. */
+int fotg_object_overlap(int device, int n, const int *ids_a, const int *ids_b, int w, int h, const float *flow,
+                        const unsigned char *mask, int ka, int kb, int *votes, long long *sent, void *stream);
+/* Step 1 on the coarse flow of a context (n x hl x wl x 2, as fotg_calc_batch returns it), upsampled and cropped on the fly, ids and
+ * mask of h_org x w_org: both outputs equal fotg_object_overlap on fotg_upsample_crop's output bit for bit, without the
+ * full-resolution flow ever being written.  FOTG_ERR_ARG also for n > max_batch and a depth-mode context. */
+int fotg_upsample_crop_object_overlap(fotg_ctx *ctx, int n, const float *coarse_flow, const int *ids_a, const int *ids_b,
+                                      const unsigned char *mask, int ka, int kb, int *votes, long long *sent, void *stream);
+int fotg_object_links(int device, int n, const int *votes, const long long *objects_a, const long long *objects_b, int ka, int kb,
+                      int min_votes, int min_frac256, int *link_ab, int *link_ba, void *stream);
+int fotg_object_tracks(int device, int T, int K, const long long *objects, const int *link_ab, const int *link_ba, int max_tracks,
+                       int *track, long long *tracks, long long *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
