@@ -2,6 +2,8 @@
 module raises -- there is no CPU or PyTorch fallback anywhere in this package."""
 import ctypes as C
 import os
+import sys
+import types
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfotg.so")
@@ -143,7 +145,6 @@ def lib():
         if exp:
             # A/B timing of experimental builds (tools/exp_*.sh): the variant is NAMED, the product library is never overwritten.  Loud,
             # because such a build may be one that is documented as producing wrong results.
-            import sys
             print("flowonthego_amd: FOTG_EXPERIMENTAL_LIB=%s replaces %s in this process" % (exp, LIB_PATH), file=sys.stderr)
             path = exp
         if not os.path.exists(path):
@@ -164,3 +165,13 @@ def check(status):
     if status != 0:
         L = lib()
         raise FotgError("fotg: %s (status %d, hip error %d)" % (L.fotg_strerror(status).decode(), status, L.fotg_last_hip_error()))
+
+
+def callable_module(name, target, func):
+    """Make the module `name` callable: calling it calls `func` of the module `target`, imported at the call.  (Importing a
+    command-line submodule such as flowonthego_amd.warp binds the package attribute of that name to the module, so
+    flowonthego_amd.warp(...) has to keep working.)"""
+    class _Callable(types.ModuleType):
+        def __call__(self, *a, **kw):
+            return getattr(__import__(target, fromlist=[func]), func)(*a, **kw)
+    sys.modules[name].__class__ = _Callable

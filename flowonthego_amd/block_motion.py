@@ -12,7 +12,8 @@ The module is callable: flowonthego_amd.block_motion(cur, ref, flow, ...) is flo
 import argparse
 import math
 import sys
-import types
+
+from ._lib import callable_module
 
 
 def main(argv=None):
@@ -67,14 +68,7 @@ def main(argv=None):
     return 0
 
 
-class _Callable(types.ModuleType):
-    """importing this submodule binds the package attribute `block_motion` to the module: calling it calls blockmotion.block_motion()"""
-    def __call__(self, *a, **kw):
-        from .blockmotion import block_motion
-        return block_motion(*a, **kw)
-
-
-sys.modules[__name__].__class__ = _Callable
+callable_module(__name__, __package__ + ".blockmotion", "block_motion")
 
 if __name__ == "__main__":
     sys.exit(main())

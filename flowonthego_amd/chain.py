@@ -6,12 +6,10 @@ the chain runs in HIP only, there is no CPU fallback.
 
 The module is callable: flowonthego_amd.chain(flows, ...) is flowonthego_amd.chain.chain(flows, ...)."""
 import ctypes as C
-import sys
-import types
 
 import torch
 
-from ._lib import FotgError, check, lib
+from ._lib import FotgError, callable_module, check, lib
 from .oflow import _dev_f32, _ptr, _stream
 
 STATS = ("valid", "occluded", "outside", "unknown", "sum_steps")
@@ -160,10 +158,4 @@ def track(ofc, frames, points=None, alpha1=0.01, alpha2=0.5, stats=False, fused=
     return upsample_crop_track_points(ofc, points, fw, bw, alpha1, alpha2, stats, bool(fused))
 
 
-class _Callable(types.ModuleType):
-    """importing this submodule binds the package attribute `chain` to the module: calling it calls chain()"""
-    def __call__(self, *a, **kw):
-        return chain(*a, **kw)
-
-
-sys.modules[__name__].__class__ = _Callable
+callable_module(__name__, __name__, "chain")

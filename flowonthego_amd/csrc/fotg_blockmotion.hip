@@ -2,39 +2,12 @@
 // kernels in blockmotion.hip.h.  Per call: one launch and, when statistics are asked for, a second small launch that folds the
 // per-block figures (the squared errors travel through stream-ordered memory of the call).  Everything is enqueued on the caller's
 // stream.
-#include "common.h"
+#include "host_call.h"
 #include "blockmotion.hip.h"
 
 using namespace fotg;
 
 namespace {
-
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  hipError_t err = hipSuccess;       // what the failing hipGetDevice / hipSetDevice returned
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if ((err = hipSetDevice(dev)) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
-
-bool overlap(const void *a_, size_t abytes, const void *b_, size_t bbytes)
-{
-  const char *a = static_cast<const char *>(a_), *b = static_cast<const char *>(b_);
-  return a < b + bbytes && b < a + abytes;
-}
 
 template <class Src, int NOC, int B>
 hipError_t launch(const dim3 &grid, hipStream_t stream, const Src &flow, const unsigned char *cur, const unsigned char *ref,
@@ -62,14 +35,16 @@ int block_motion_batch(int device, int n, const Src &flow, const void *flow_mem,
   if ((block != 8 && block != 16 && block != 32) || refine < 0 || refine > 3) return FOTG_ERR_ARG;
   if (!flow_mem || !cur || !ref || !mv || !cost || !kind) return FOTG_ERR_ARG;
   const size_t fbytes = (size_t)n * w * h * channels;
-  if (pred && (overlap(pred, fbytes, cur, fbytes) || overlap(pred, fbytes, ref, fbytes))) return FOTG_ERR_ARG;   // other blocks read them
+  const Span out[1] = {{pred, fbytes}}, in[2] = {{cur, fbytes}, {ref, fbytes}};
+  if (overlap_any(out, in)) return FOTG_ERR_ARG;                                     // other blocks read them
   const int bw = (w + block - 1) / block, bh = (h + block - 1) / block, nblk = bw * bh;
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   hipStream_t stream = (hipStream_t)stream_;
   unsigned *sse = nullptr;
-  hipError_t e = hipSuccess;
-  if (stats) e = hipMallocAsync((void **)&sse, (size_t)n * nblk * sizeof(unsigned), stream);
+  Scratch mem(stream);
+  if (stats) mem.get(&sse, (size_t)n * nblk * sizeof(unsigned));
+  hipError_t e = mem.err;
   if (e == hipSuccess) {
     const dim3 grid((unsigned)((nblk + BM_WAVES - 1) / BM_WAVES), (unsigned)n);
     if (channels == 1)
@@ -81,11 +56,7 @@ int block_motion_batch(int device, int n, const Src &flow, const void *flow_mem,
     blockmv_fold_kernel<<<dim3((unsigned)n), BM_THREADS, 0, stream>>>(cost, kind, sse, nblk, stats);
     e = hipGetLastError();
   }
-  if (sse) {
-    const hipError_t ef = hipFreeAsync(sse, stream);
-    if (e == hipSuccess) e = ef;
-  }
-  return e == hipSuccess ? FOTG_OK : hip_fail(e);
+  return mem.finish(e);
 }
 
 }  // namespace
@@ -105,11 +76,9 @@ int fotg_upsample_crop_block_motion(fotg_ctx *ctx, int n, const float *coarse_fl
                                     unsigned char *kind, unsigned char *pred, long long *stats, void *stream)
 {
   CtxUpsampleGeom g;
-  if (!ctx || !coarse_flow || ctx_upsample_geom(ctx, &g) != FOTG_OK) return FOTG_ERR_ARG;
-  if (n < 1 || n > g.max_batch || g.nch != 2) return FOTG_ERR_ARG;
-  const UpsampleSrc f{coarse_flow, (long)g.wl * g.hl * 2, g.wl, g.hl, g.sc_l, g.x0, g.y0};
-  return block_motion_batch(g.device, n, f, coarse_flow, cur, ref, g.w_org, g.h_org, channels, mask, block, refine, mv, cost, kind,
-                            pred, stats, stream);
+  if (!fused_geom(ctx, n, coarse_flow, &g)) return FOTG_ERR_ARG;
+  return block_motion_batch(g.device, n, upsample_src(g, coarse_flow), coarse_flow, cur, ref, g.w_org, g.h_org, channels, mask, block,
+                            refine, mv, cost, kind, pred, stats, stream);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@
 #include <mutex>
 #include <new>
 #include <type_traits>
-#include "common.h"
+#include "host_call.h"
 #include "pipe_tickets.h"
 #include "pipe_queues.h"
 #include "pyramid.hip.h"
@@ -35,20 +35,7 @@ static thread_local int g_last_hip = 0;
   } while (0)
 #define LAUNCHCHK() HIPCHK(hipGetLastError())
 
-// every entry point runs on the context's device and leaves the caller's current device as it found it
-struct DevGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if (hipSetDevice(dev) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
+// every entry point runs on the context's device and leaves the caller's current device as it found it (DevGuard: host_call.h)
 #define ON_DEVICE(dev)                                                              \
   DevGuard dev_guard_(dev);                                                         \
   if (!dev_guard_.ok) { g_last_hip = (int)hipGetLastError(); return FOTG_ERR_HIP; }

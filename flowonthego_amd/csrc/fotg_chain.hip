@@ -1,50 +1,12 @@
 // fotg_chain.hip -- C-ABI of flow chaining (include/fotg.h fotg_flow_chain / fotg_track_points and their fused forms), kernels in
 // chain.hip.h.  Per call: zero the statistics (when asked for), one launch that walks all T steps of every chain.  Asynchronous on
 // the caller's stream; no host synchronisation.
-#include "common.h"
+#include "host_call.h"
 #include "chain.hip.h"
 
 using namespace fotg;
 
 namespace {
-
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  hipError_t err = hipSuccess;       // what the failing hipGetDevice / hipSetDevice returned
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if ((err = hipSetDevice(dev)) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
-
-struct Span { const void *p; size_t bytes; };
-
-bool overlap(const Span &a, const Span &b)
-{
-  if (!a.p || !b.p) return false;
-  const char *x = static_cast<const char *>(a.p), *y = static_cast<const char *>(b.p);
-  return x < y + b.bytes && y < x + a.bytes;
-}
-
-bool any_overlap(const Span *out, int n_out, const Span *in, int n_in)
-{
-  for (int i = 0; i < n_out; ++i)
-    for (int j = 0; j < n_in; ++j)
-      if (overlap(out[i], in[j])) return true;
-  return false;
-}
 
 // the size checks every form shares
 bool chain_args_ok(int n_seq, int T, int w, int h)
@@ -63,7 +25,7 @@ int chain_dense(int device, int n_seq, int T, const Src &fw, const Src &bw, bool
   const size_t hw = (size_t)w * h, np = (size_t)n_seq * hw;
   const Span out[4] = {{total, np * 8}, {code, np}, {steps, np * 4}, {stats, (size_t)n_seq * CHAIN_NSTAT * 8}};
   const Span in[2] = {{fw.flow, in_bytes}, {has_bw ? bw.flow : nullptr, in_bytes}};
-  if (any_overlap(out, 4, in, 2)) return FOTG_ERR_ARG;
+  if (overlap_any(out, in)) return FOTG_ERR_ARG;              // (outputs against inputs only)
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   hipStream_t stream = (hipStream_t)stream_;
@@ -89,7 +51,7 @@ int chain_points(int device, int n_seq, int T, const Src &fw, const Src &bw, boo
   const size_t np = (size_t)n_seq * P;
   const Span out[4] = {{traj, np * ((size_t)T + 1) * 8}, {code, np}, {steps, np * 4}, {stats, (size_t)n_seq * CHAIN_NSTAT * 8}};
   const Span in[3] = {{fw.flow, in_bytes}, {has_bw ? bw.flow : nullptr, in_bytes}, {pts, np * 8}};
-  if (any_overlap(out, 4, in, 3)) return FOTG_ERR_ARG;
+  if (overlap_any(out, in)) return FOTG_ERR_ARG;
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   hipStream_t stream = (hipStream_t)stream_;
@@ -104,18 +66,6 @@ int chain_points(int device, int n_seq, int T, const Src &fw, const Src &bw, boo
     chain_points_kernel<Src, false><<<grid, CHAIN_THREADS, 0, stream>>>(fw, fw, T, w, h, alpha1, alpha2, P, pts, traj, code, steps, stats);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? FOTG_OK : hip_fail(e);
-}
-
-// the context's geometry for a chain of T of its coarse flows: one sequence, the batch index is the step
-bool fused_geom(fotg_ctx *ctx, int T, const float *coarse, CtxUpsampleGeom *g)
-{
-  if (!ctx || !coarse || ctx_upsample_geom(ctx, g) != FOTG_OK) return false;
-  return T >= 1 && T <= g->max_batch && g->nch == 2;
-}
-
-UpsampleSrc fused_src(const CtxUpsampleGeom &g, const float *flow)
-{
-  return UpsampleSrc{flow, (long)g.wl * g.hl * 2, g.wl, g.hl, g.sc_l, g.x0, g.y0};
 }
 
 }  // namespace
@@ -144,10 +94,10 @@ int fotg_track_points(int device, int n_seq, int T, const float *flows, const fl
 int fotg_upsample_crop_flow_chain(fotg_ctx *ctx, int T, const float *coarse_flows, const float *coarse_bw, float alpha1, float alpha2,
                                   float *total, unsigned char *code, int *steps, unsigned long long *stats, void *stream)
 {
-  CtxUpsampleGeom g;
+  CtxUpsampleGeom g;                 // a chain of T of the context's coarse flows: one sequence, the batch index is the step
   if (!fused_geom(ctx, T, coarse_flows, &g)) return FOTG_ERR_ARG;
   const size_t in_bytes = (size_t)T * g.wl * g.hl * 2 * sizeof(float);
-  return chain_dense(g.device, 1, T, fused_src(g, coarse_flows), fused_src(g, coarse_bw), coarse_bw != nullptr, in_bytes, g.w_org,
+  return chain_dense(g.device, 1, T, upsample_src(g, coarse_flows), upsample_src(g, coarse_bw), coarse_bw != nullptr, in_bytes, g.w_org,
                      g.h_org, alpha1, alpha2, total, code, steps, stats, stream);
 }
 
@@ -158,7 +108,7 @@ int fotg_upsample_crop_track_points(fotg_ctx *ctx, int T, const float *coarse_fl
   CtxUpsampleGeom g;
   if (!fused_geom(ctx, T, coarse_flows, &g)) return FOTG_ERR_ARG;
   const size_t in_bytes = (size_t)T * g.wl * g.hl * 2 * sizeof(float);
-  return chain_points(g.device, 1, T, fused_src(g, coarse_flows), fused_src(g, coarse_bw), coarse_bw != nullptr, in_bytes, g.w_org,
+  return chain_points(g.device, 1, T, upsample_src(g, coarse_flows), upsample_src(g, coarse_bw), coarse_bw != nullptr, in_bytes, g.w_org,
                       g.h_org, alpha1, alpha2, P, pts, traj, code, steps, stats, stream);
 }
 

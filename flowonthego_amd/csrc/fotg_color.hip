@@ -1,32 +1,12 @@
 // fotg_color.hip -- C-ABI of the Middlebury flow colour code (include/fotg.h fotg_flow_color / fotg_upsample_crop_color), kernels in
 // flowcolor.hip.h.  Per batch: zero the per-image keys, range pass, colour pass, and (when the caller asked for them) the keys
 // turned into the printed statistics in place.  Asynchronous on the caller's stream; no host synchronisation.
-#include "common.h"
+#include "host_call.h"
 #include "flowcolor.hip.h"
 
 using namespace fotg;
 
 namespace {
-
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if (hipSetDevice(dev) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
 
 // range + colour launches over a batch of n images of w x h pixels, whatever Src reads them from
 template <class Src>
@@ -40,10 +20,8 @@ int color_batch(int device, int n, const Src &src, int w, int h, float maxmotion
   hipStream_t stream = (hipStream_t)stream_;
   // per-image keys: the caller's stats buffer (decoded in place at the end), or stream-ordered memory of our own
   unsigned *keys = reinterpret_cast<unsigned *>(stats);
-  if (!keys) {
-    const hipError_t e = hipMallocAsync((void **)&keys, (size_t)n * FC_NSTAT * sizeof(unsigned), stream);
-    if (e != hipSuccess) return hip_fail(e);
-  }
+  Scratch mem(stream);
+  if (!keys && !mem.get(&keys, (size_t)n * FC_NSTAT * sizeof(unsigned))) return mem.finish(mem.err);
   hipError_t e = hipMemsetAsync(keys, 0, (size_t)n * FC_NSTAT * sizeof(unsigned), stream);
   if (e == hipSuccess) {
     // range pass: at least 4 pixels per thread, about 4096 workgroups for the batch (16 per CU)
@@ -54,11 +32,7 @@ int color_batch(int device, int n, const Src &src, int w, int h, float maxmotion
     if (stats) flow_stats_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, stream>>>(n, keys);
     e = hipGetLastError();
   }
-  if (!stats) {
-    const hipError_t ef = hipFreeAsync(keys, stream);
-    if (e == hipSuccess) e = ef;
-  }
-  return e == hipSuccess ? FOTG_OK : hip_fail(e);
+  return mem.finish(e);
 }
 
 }  // namespace
@@ -74,10 +48,8 @@ int fotg_flow_color(int device, int n, const float *flow, int w, int h, float ma
 int fotg_upsample_crop_color(fotg_ctx *ctx, int n, const float *flow, float maxmotion, unsigned char *rgb, float *stats, void *stream)
 {
   CtxUpsampleGeom g;
-  if (!ctx || !flow || !rgb || ctx_upsample_geom(ctx, &g) != FOTG_OK) return FOTG_ERR_ARG;
-  if (n < 1 || n > g.max_batch || g.nch != 2) return FOTG_ERR_ARG;
-  const UpsampleSrc src{flow, (long)g.wl * g.hl * 2, g.wl, g.hl, g.sc_l, g.x0, g.y0};
-  return color_batch(g.device, n, src, g.w_org, g.h_org, maxmotion, rgb, stats, stream);
+  if (!rgb || !fused_geom(ctx, n, flow, &g)) return FOTG_ERR_ARG;
+  return color_batch(g.device, n, upsample_src(g, flow), g.w_org, g.h_org, maxmotion, rgb, stats, stream);
 }
 
 }  // extern "C"

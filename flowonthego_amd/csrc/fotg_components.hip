@@ -2,42 +2,12 @@
 // components.hip.h.  Per call seven launches on the caller's stream; the parent array (unless `labels` is asked for), the per-pixel
 // area array and the chunk counts are the call's own memory, taken from and returned to the stream's pool.  Nothing synchronises
 // with the host.
-#include "common.h"
+#include "host_call.h"
 #include "components.hip.h"
 
 using namespace fotg;
 
 namespace {
-
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  hipError_t err = hipSuccess;
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if ((err = hipSetDevice(dev)) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
-
-struct Span { const void *p; size_t bytes; };
-
-bool overlap(const Span &a, const Span &b)
-{
-  if (!a.p || !b.p) return false;
-  const char *x = static_cast<const char *>(a.p), *y = static_cast<const char *>(b.p);
-  return x < y + b.bytes && y < x + a.bytes;
-}
 
 }  // namespace
 
@@ -58,24 +28,19 @@ int fotg_label_components(int device, int n, const unsigned char *code, int w, i
   const Span out[4] = {{labels, n * hw * 4}, {ids, n * hw * 4}, {objects, (size_t)n * max_objects * COMP_NREC * 8},
                        {stats, (size_t)n * COMP_NSTAT * 8}};
   const Span in[2] = {{code, n * hw}, {values, n * hw * 8}};
-  for (int i = 0; i < 4; ++i) {
-    for (int j = 0; j < 2; ++j)
-      if (overlap(out[i], in[j])) return FOTG_ERR_ARG;
-    for (int j = i + 1; j < 4; ++j)
-      if (overlap(out[i], out[j])) return FOTG_ERR_ARG;
-  }
+  if (overlap_any(out, in) || overlap_among(out)) return FOTG_ERR_ARG;
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   hipStream_t stream = (hipStream_t)stream_;
   // the call's memory: [the parents, n h w] the areas, n h w; the chunk counts, n chunks
   const size_t ints = (labels ? 0 : n * hw) + n * hw + (size_t)n * chunks;
   int *ws = nullptr;
-  hipError_t e = hipMallocAsync((void **)&ws, ints * sizeof(int), stream);
-  if (e != hipSuccess) return hip_fail(e);
+  Scratch mem(stream);
+  if (!mem.get(&ws, ints * sizeof(int))) return mem.finish(mem.err);
   int *par = labels ? labels : ws;
   int *aux = labels ? ws : ws + n * hw;
   int *chunk_cnt = aux + n * hw;
-  e = hipMemsetAsync(objects, 0, out[2].bytes, stream);
+  hipError_t e = hipMemsetAsync(objects, 0, out[2].bytes, stream);
   if (e == hipSuccess && stats) e = hipMemsetAsync(stats, 0, out[3].bytes, stream);
   if (e == hipSuccess) {
     const bool conn8 = connectivity == 8;
@@ -95,9 +60,7 @@ int fotg_label_components(int device, int n, const unsigned char *code, int w, i
       comp_reduce_kernel<false><<<tgrid, COMP_THREADS, 0, stream>>>(par, aux, nullptr, n, w, h, ntx, max_objects, objects, ids);
     e = hipGetLastError();
   }
-  const hipError_t ef = hipFreeAsync(ws, stream);
-  if (e == hipSuccess) e = ef;
-  return e == hipSuccess ? FOTG_OK : hip_fail(e);
+  return mem.finish(e);
 }
 
 int fotg_components_tile(int *tw, int *th)

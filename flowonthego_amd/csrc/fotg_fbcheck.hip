@@ -1,33 +1,12 @@
 // fotg_fbcheck.hip -- C-ABI of the forward-backward consistency check (include/fotg.h fotg_fb_check /
 // fotg_upsample_crop_fb_check), kernel in fbcheck.hip.h.  Per call: zero the counts (when asked for), one launch for both
 // directions of every pair.  Asynchronous on the caller's stream; no host synchronisation.
-#include "common.h"
+#include "host_call.h"
 #include "fbcheck.hip.h"
 
 using namespace fotg;
 
 namespace {
-
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  hipError_t err = hipSuccess;       // what the failing hipGetDevice / hipSetDevice returned
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if ((err = hipSetDevice(dev)) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
 
 template <class Src>
 int fb_batch(int device, int n, const Src &fw, const Src &bw, int w, int h, float alpha1, float alpha2, unsigned char *mask,
@@ -64,11 +43,9 @@ int fotg_upsample_crop_fb_check(fotg_ctx *ctx, int n, const float *flow, const f
                                 unsigned char *mask, unsigned char *mask_bw, unsigned *counts, void *stream)
 {
   CtxUpsampleGeom g;
-  if (!ctx || !flow || !flow_bw || ctx_upsample_geom(ctx, &g) != FOTG_OK) return FOTG_ERR_ARG;
-  if (n < 1 || n > g.max_batch || g.nch != 2) return FOTG_ERR_ARG;
-  const long in_stride = (long)g.wl * g.hl * 2;
-  const UpsampleSrc fw{flow, in_stride, g.wl, g.hl, g.sc_l, g.x0, g.y0}, bw{flow_bw, in_stride, g.wl, g.hl, g.sc_l, g.x0, g.y0};
-  return fb_batch(g.device, n, fw, bw, g.w_org, g.h_org, alpha1, alpha2, mask, mask_bw, counts, stream);
+  if (!flow_bw || !fused_geom(ctx, n, flow, &g)) return FOTG_ERR_ARG;
+  return fb_batch(g.device, n, upsample_src(g, flow), upsample_src(g, flow_bw), g.w_org, g.h_org, alpha1, alpha2, mask, mask_bw, counts,
+                  stream);
 }
 
 }  // extern "C"

@@ -5,39 +5,12 @@
 // The spatial table travels by value in the kernel arguments.  Everything is enqueued on the caller's stream; the host array is
 // consumed before the call returns.
 #include <cmath>
-#include "common.h"
+#include "host_call.h"
 #include "flowfilter.hip.h"
 
 using namespace fotg;
 
 namespace {
-
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  hipError_t err = hipSuccess;       // what the failing hipGetDevice / hipSetDevice returned
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if ((err = hipSetDevice(dev)) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
-
-bool overlap(const void *a_, size_t abytes, const void *b_, size_t bbytes)
-{
-  const char *a = static_cast<const char *>(a_), *b = static_cast<const char *>(b_);
-  return a < b + bbytes && b < a + abytes;
-}
 
 template <class Src, class T, int NOC>
 hipError_t launch_pass(const dim3 &grid, hipStream_t stream, const Src &flow, const float *prev, const T *guide,
@@ -70,7 +43,7 @@ int filter_batch(int device, int n, const Src &flow, const void *flow_mem, size_
   const long blocks = tiles_x * tiles_y;
   if (blocks > 0x7fffffffL || tiles_y > 65535 || n > 65535) return FOTG_ERR_ARG;
   const size_t vbytes = (size_t)n * hw * 2 * sizeof(float);
-  if (out && overlap(flow_mem, flow_bytes, out, vbytes)) return FOTG_ERR_ARG;       // a window reads what a neighbour's thread writes
+  if (overlap(Span{flow_mem, flow_bytes}, Span{out, vbytes})) return FOTG_ERR_ARG;  // a window reads what a neighbour's thread writes
   const float scale = 1.0f / (tau * (float)channels);
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
@@ -81,15 +54,15 @@ int filter_batch(int device, int n, const Src &flow, const void *flow_mem, size_
   float *tmp[2] = {nullptr, nullptr};
   unsigned char *pc[2] = {nullptr, nullptr};
   WarpPartial *part = nullptr;
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMallocAsync(p, bytes, stream); };
+  Scratch mem(stream);
   if (iters > 1) {
-    alloc((void **)&tmp[0], vbytes);
-    if (!out && iters > 2) alloc((void **)&tmp[1], vbytes);
-    alloc((void **)&pc[0], (size_t)n * hw);
-    if (iters > 2) alloc((void **)&pc[1], (size_t)n * hw);
+    mem.get(&tmp[0], vbytes);
+    if (!out && iters > 2) mem.get(&tmp[1], vbytes);
+    mem.get(&pc[0], (size_t)n * hw);
+    if (iters > 2) mem.get(&pc[1], (size_t)n * hw);
   }
-  if (stats) alloc((void **)&part, (size_t)n * blocks * sizeof(WarpPartial));
+  if (stats) mem.get(&part, (size_t)n * blocks * sizeof(WarpPartial));
+  hipError_t e = mem.err;
 
   const dim3 grid((unsigned)tiles_x, (unsigned)tiles_y, (unsigned)n);
   const float *prev = nullptr;
@@ -112,12 +85,7 @@ int filter_batch(int device, int n, const Src &flow, const void *flow_mem, size_
     flowfilter_fold_kernel<<<dim3((unsigned)n), WARP_THREADS, 0, stream>>>(part, (int)blocks, stats);
     e = hipGetLastError();
   }
-  for (void *p : {(void *)part, (void *)pc[1], (void *)pc[0], (void *)tmp[1], (void *)tmp[0]}) {
-    if (!p) continue;
-    const hipError_t ef = hipFreeAsync(p, stream);
-    if (e == hipSuccess) e = ef;
-  }
-  return e == hipSuccess ? FOTG_OK : hip_fail(e);
+  return mem.finish(e);
 }
 
 template <class T>
@@ -134,11 +102,9 @@ int filter_fused(fotg_ctx *ctx, int n, const float *coarse, const T *guide, int 
                  const float *spatial, float tau, int iters, float *out, unsigned char *code, double *stats, void *stream)
 {
   CtxUpsampleGeom g;
-  if (!ctx || !coarse || ctx_upsample_geom(ctx, &g) != FOTG_OK) return FOTG_ERR_ARG;
-  if (n < 1 || n > g.max_batch || g.nch != 2) return FOTG_ERR_ARG;
-  const UpsampleSrc f{coarse, (long)g.wl * g.hl * 2, g.wl, g.hl, g.sc_l, g.x0, g.y0};
-  return filter_batch(g.device, n, f, coarse, (size_t)n * g.wl * g.hl * 2 * sizeof(float), guide, g.w_org, g.h_org, channels, mask,
-                      R, spatial, tau, iters, out, code, stats, stream);
+  if (!fused_geom(ctx, n, coarse, &g)) return FOTG_ERR_ARG;
+  return filter_batch(g.device, n, upsample_src(g, coarse), coarse, (size_t)n * g.wl * g.hl * 2 * sizeof(float), guide, g.w_org,
+                      g.h_org, channels, mask, R, spatial, tau, iters, out, code, stats, stream);
 }
 
 }  // namespace

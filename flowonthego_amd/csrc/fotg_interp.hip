@@ -5,7 +5,7 @@
 // The key planes take 16 bytes per pixel and image (two directions of 64-bit keys): the batch is processed in chunks of as many
 // images as fit INTERP_KEY_BYTES (256 MiB; one image when a single one is larger), so a 64 x 1080p call holds 8 images' planes
 // at a time instead of 2.1 GB.  Asynchronous on the caller's stream; no host synchronisation.
-#include "common.h"
+#include "host_call.h"
 #include "fbcheck.hip.h"
 #include "interp.hip.h"
 
@@ -15,37 +15,9 @@ namespace {
 
 const size_t INTERP_KEY_BYTES = (size_t)256 << 20;
 
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  hipError_t err = hipSuccess;       // what the failing hipGetDevice / hipSetDevice returned
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if ((err = hipSetDevice(dev)) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
-
 // the source of the images first, first + 1, ... of a batch
 DenseSrc from_image(const DenseSrc &s, long first, long hw) { return DenseSrc{s.flow + 2 * first * hw}; }
 UpsampleSrc from_image(UpsampleSrc s, long first, long) { s.flow += first * s.in_stride; return s; }
-
-template <class T>
-bool overlaps(const T *a, const T *b, size_t bytes)
-{
-  const char *p = reinterpret_cast<const char *>(a), *q = reinterpret_cast<const char *>(b);
-  return p < q + bytes && q < p + bytes;
-}
 
 template <class Src, class T, int NOC>
 hipError_t launch_chunk(int n, const Src &fw, const Src &bw, const T *I0, const T *I1, const unsigned char *mF, const unsigned char *mB,
@@ -71,10 +43,9 @@ int interp_batch(int device, int n, const Src &fw, const Src &bw, const T *I0, c
   const long hw = (long)w * h;
   if (hw > 0xffffffffL || n > 65535) return FOTG_ERR_ARG;          // the key holds the source index in 32 bits
   const long blocks = ((hw + 3) / 4 + WARP_THREADS - 1) / WARP_THREADS;
-  if (dst) {                         // the taps of a pixel are read after other pixels have been written: not in place
-    const size_t bytes = (size_t)n * hw * channels * sizeof(T);
-    if (overlaps(I0, dst, bytes) || overlaps(I1, dst, bytes)) return FOTG_ERR_ARG;
-  }
+  const size_t bytes = (size_t)n * hw * channels * sizeof(T);
+  const Span out[1] = {{dst, bytes}}, in[2] = {{I0, bytes}, {I1, bytes}};
+  if (overlap_any(out, in)) return FOTG_ERR_ARG;      // the taps of a pixel are read after other pixels have been written: not in place
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   hipStream_t stream = (hipStream_t)stream_;
@@ -83,9 +54,11 @@ int interp_batch(int device, int n, const Src &fw, const Src &bw, const T *I0, c
   interp_key *keys = nullptr;
   unsigned char *own_masks = nullptr;
   WarpPartial *part = nullptr;
-  hipError_t e = hipMallocAsync((void **)&keys, (size_t)chunk * 2 * hw * sizeof(interp_key), stream);
-  if (e == hipSuccess && !mask_fw) e = hipMallocAsync((void **)&own_masks, (size_t)chunk * 2 * hw, stream);
-  if (e == hipSuccess && stats) e = hipMallocAsync((void **)&part, (size_t)n * blocks * sizeof(WarpPartial), stream);
+  Scratch mem(stream);
+  mem.get(&keys, (size_t)chunk * 2 * hw * sizeof(interp_key));
+  if (!mask_fw) mem.get(&own_masks, (size_t)chunk * 2 * hw);
+  if (stats) mem.get(&part, (size_t)n * blocks * sizeof(WarpPartial));
+  hipError_t e = mem.err;
   for (long first = 0; e == hipSuccess && first < n; first += chunk) {
     const int m = (int)(n - first < chunk ? n - first : chunk);
     const Src f = from_image(fw, first, hw), b = from_image(bw, first, hw);
@@ -103,16 +76,8 @@ int interp_batch(int device, int n, const Src &fw, const Src &bw, const T *I0, c
     e = channels == 1 ? launch_chunk<Src, T, 1>(m, f, b, I0 + img, I1 + img, mF, mB, keys, r, w, h, t, d, c, p, (unsigned)blocks, stream)
                       : launch_chunk<Src, T, 3>(m, f, b, I0 + img, I1 + img, mF, mB, keys, r, w, h, t, d, c, p, (unsigned)blocks, stream);
   }
-  if (e == hipSuccess && stats) {
-    e = warp_fold(part, (int)blocks, n, stats, stream);
-  }
-  void *owned[3] = {keys, own_masks, part};
-  for (void *o : owned)
-    if (o) {
-      const hipError_t ef = hipFreeAsync(o, stream);
-      if (e == hipSuccess) e = ef;
-    }
-  return e == hipSuccess ? FOTG_OK : hip_fail(e);
+  if (e == hipSuccess && stats) e = warp_fold(part, (int)blocks, n, stats, stream);
+  return mem.finish(e);
 }
 
 template <class T>
@@ -134,10 +99,8 @@ int interp_fused(fotg_ctx *ctx, int n, const float *flow_fw, const float *flow_b
   if (!ctx || !flow_fw || !flow_bw || ctx_upsample_geom(ctx, &g) != FOTG_OK) return FOTG_ERR_ARG;
   if (!g.bidir) return FOTG_ERR_UNSUPPORTED;
   if (n < 1 || n > g.max_batch || g.nch != 2) return FOTG_ERR_ARG;
-  const long in_stride = (long)g.wl * g.hl * 2;
-  const UpsampleSrc fw{flow_fw, in_stride, g.wl, g.hl, g.sc_l, g.x0, g.y0}, bw{flow_bw, in_stride, g.wl, g.hl, g.sc_l, g.x0, g.y0};
-  return interp_batch(g.device, n, fw, bw, I0, I1, g.w_org, g.h_org, channels, t, mask_fw, mask_bw, alpha1, alpha2, ref, dst, code,
-                      stats, stream);
+  return interp_batch(g.device, n, upsample_src(g, flow_fw), upsample_src(g, flow_bw), I0, I1, g.w_org, g.h_org, channels, t, mask_fw,
+                      mask_bw, alpha1, alpha2, ref, dst, code, stats, stream);
 }
 
 }  // namespace

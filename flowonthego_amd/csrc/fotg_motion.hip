@@ -3,7 +3,7 @@
 // then the final pass where codes, residuals or counts are asked for.  The accumulators and the parameters stay on the device;
 // everything is asynchronous on the caller's stream, nothing synchronises with the host.
 #include <atomic>
-#include "common.h"
+#include "host_call.h"
 #include "motion.hip.h"
 
 using namespace fotg;
@@ -14,36 +14,6 @@ namespace {
 // motion_fold_kernel.  Same bits either way (integer sums); the default is the one that measured faster, in every form, by
 // 0.06 .. 0.09 ms per pass over 64 x 1080p: the fold.
 std::atomic<int> g_ending{1};
-
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  hipError_t err = hipSuccess;       // what the failing hipGetDevice / hipSetDevice returned
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if ((err = hipSetDevice(dev)) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
-
-struct Span { const void *p; size_t bytes; };
-
-bool overlap(const Span &a, const Span &b)
-{
-  if (!a.p || !b.p) return false;
-  const char *x = static_cast<const char *>(a.p), *y = static_cast<const char *>(b.p);
-  return x < y + b.bytes && y < x + a.bytes;
-}
 
 template <class Src, int PASS>
 void launch_pass(dim3 grid, hipStream_t stream, const Src &flow, const unsigned char *mask, int w, int h, const double *params,
@@ -62,12 +32,7 @@ int fit_batch(int device, int n, const Src &flow, size_t in_bytes, const unsigne
   const Span out[5] = {{params, (size_t)n * 6 * 8}, {code, n * hw}, {residual, n * hw * 8}, {stats, (size_t)n * MOTION_NSTAT * 8},
                        {sums, (size_t)n * MOTION_NSUM * 8}};
   const Span in[2] = {{flow.flow, in_bytes}, {mask, n * hw}};
-  for (int i = 0; i < 5; ++i) {
-    for (int j = 0; j < 2; ++j)
-      if (overlap(out[i], in[j])) return FOTG_ERR_ARG;
-    for (int j = i + 1; j < 5; ++j)
-      if (overlap(out[i], out[j])) return FOTG_ERR_ARG;
-  }
+  if (overlap_any(out, in) || overlap_among(out)) return FOTG_ERR_ARG;
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   hipStream_t stream = (hipStream_t)stream_;
@@ -77,10 +42,10 @@ int fit_batch(int device, int n, const Src &flow, size_t in_bytes, const unsigne
   // the call's memory: n x 12 accumulators, n `bad` flags, then (fold ending) the per-workgroup partials
   const size_t head = (size_t)n * (MOTION_NSUM + 1);
   long long *ws = nullptr;
-  hipError_t e = hipMallocAsync((void **)&ws, (head + (fold ? (size_t)n * blocks * MOTION_NSUM : 0)) * sizeof(long long), stream);
-  if (e != hipSuccess) return hip_fail(e);
+  Scratch mem(stream);
+  if (!mem.get(&ws, (head + (fold ? (size_t)n * blocks * MOTION_NSUM : 0)) * sizeof(long long))) return mem.finish(mem.err);
   long long *acc = ws, *bad = ws + (size_t)n * MOTION_NSUM, *part = fold ? ws + head : nullptr;
-  e = hipMemsetAsync(ws, 0, head * sizeof(long long), stream);
+  hipError_t e = hipMemsetAsync(ws, 0, head * sizeof(long long), stream);
   if (e == hipSuccess) e = hipMemsetAsync(params, 0, out[0].bytes, stream);
   if (e == hipSuccess && stats) e = hipMemsetAsync(stats, 0, out[3].bytes, stream);
   const float thresh2 = thresh * thresh;
@@ -102,9 +67,7 @@ int fit_batch(int device, int n, const Src &flow, size_t in_bytes, const unsigne
     if (fold && stats) motion_fold_kernel<4><<<dim3((unsigned)n), MOTION_THREADS, 0, stream>>>(part, blocks, stats, MOTION_NSTAT);
     e = hipGetLastError();
   }
-  const hipError_t ef = hipFreeAsync(ws, stream);
-  if (e == hipSuccess) e = ef;
-  return e == hipSuccess ? FOTG_OK : hip_fail(e);
+  return mem.finish(e);
 }
 
 }  // namespace
@@ -124,11 +87,9 @@ int fotg_upsample_crop_fit_motion(fotg_ctx *ctx, int n, const float *coarse_flow
                                   void *stream)
 {
   CtxUpsampleGeom g;
-  if (!ctx || !coarse_flow || ctx_upsample_geom(ctx, &g) != FOTG_OK) return FOTG_ERR_ARG;
-  if (n < 1 || n > g.max_batch || g.nch != 2) return FOTG_ERR_ARG;
-  const UpsampleSrc f{coarse_flow, (long)g.wl * g.hl * 2, g.wl, g.hl, g.sc_l, g.x0, g.y0};
-  return fit_batch(g.device, n, f, (size_t)n * g.wl * g.hl * 2 * sizeof(float), mask, g.w_org, g.h_org, model, iters, thresh, params,
-                   code, residual, stats, sums, stream);
+  if (!fused_geom(ctx, n, coarse_flow, &g)) return FOTG_ERR_ARG;
+  return fit_batch(g.device, n, upsample_src(g, coarse_flow), (size_t)n * g.wl * g.hl * 2 * sizeof(float), mask, g.w_org, g.h_org,
+                   model, iters, thresh, params, code, residual, stats, sums, stream);
 }
 
 int fotg_motion_flow(int device, int n, const double *params, int w, int h, float *flow, void *stream)

@@ -1,54 +1,12 @@
 // fotg_objtracks.hip -- C-ABI of the object tracks (include/fotg.h fotg_object_overlap / fotg_upsample_crop_object_overlap /
 // fotg_object_links / fotg_object_tracks), kernels in objtracks.hip.h.  Per call: the clearing of the outputs that are accumulated
 // into, and one launch.  Everything is enqueued on the caller's stream.
-#include "common.h"
+#include "host_call.h"
 #include "objtracks.hip.h"
 
 using namespace fotg;
 
 namespace {
-
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  hipError_t err = hipSuccess;       // what the failing hipGetDevice / hipSetDevice returned
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if ((err = hipSetDevice(dev)) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
-
-struct Span { const void *p; size_t bytes; };
-
-bool overlap(const Span &a, const Span &b)
-{
-  if (!a.p || !b.p) return false;
-  const char *x = static_cast<const char *>(a.p), *y = static_cast<const char *>(b.p);
-  return x < y + b.bytes && y < x + a.bytes;
-}
-
-template <int NO, int NI>
-bool any_overlap(const Span (&out)[NO], const Span (&in)[NI])
-{
-  for (int i = 0; i < NO; ++i) {
-    for (int j = 0; j < NI; ++j)
-      if (overlap(out[i], in[j])) return true;
-    for (int j = i + 1; j < NO; ++j)
-      if (overlap(out[i], out[j])) return true;
-  }
-  return false;
-}
 
 bool aligned(const void *p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
 
@@ -63,7 +21,7 @@ int overlap_batch(int device, int n, const Src &flow, const void *flow_mem, size
   const size_t px = (size_t)n * w * h;
   const Span out[2] = {{votes, (size_t)n * ka * kb * sizeof(int)}, {sent, (size_t)n * ka * OT_NSENT * sizeof(long long)}};
   const Span in[4] = {{ids_a, px * sizeof(int)}, {ids_b, px * sizeof(int)}, {flow_mem, flow_bytes}, {mask, px}};
-  if (any_overlap(out, in)) return FOTG_ERR_ARG;
+  if (overlap_any(out, in) || overlap_among(out)) return FOTG_ERR_ARG;
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   hipStream_t stream = (hipStream_t)stream_;
@@ -93,11 +51,9 @@ int fotg_upsample_crop_object_overlap(fotg_ctx *ctx, int n, const float *coarse_
                                       const unsigned char *mask, int ka, int kb, int *votes, long long *sent, void *stream)
 {
   CtxUpsampleGeom g;
-  if (!ctx || !coarse_flow || ctx_upsample_geom(ctx, &g) != FOTG_OK) return FOTG_ERR_ARG;
-  if (n < 1 || n > g.max_batch || g.nch != 2) return FOTG_ERR_ARG;
-  const UpsampleSrc f{coarse_flow, (long)g.wl * g.hl * 2, g.wl, g.hl, g.sc_l, g.x0, g.y0};
-  return overlap_batch(g.device, n, f, coarse_flow, (size_t)n * g.wl * g.hl * 2 * sizeof(float), false, ids_a, ids_b, g.w_org, g.h_org,
-                       mask, ka, kb, votes, sent, stream);
+  if (!fused_geom(ctx, n, coarse_flow, &g)) return FOTG_ERR_ARG;
+  return overlap_batch(g.device, n, upsample_src(g, coarse_flow), coarse_flow, (size_t)n * g.wl * g.hl * 2 * sizeof(float), false,
+                       ids_a, ids_b, g.w_org, g.h_org, mask, ka, kb, votes, sent, stream);
 }
 
 int fotg_object_links(int device, int n, const int *votes, const long long *objects_a, const long long *objects_b, int ka, int kb,
@@ -109,7 +65,7 @@ int fotg_object_links(int device, int n, const int *votes, const long long *obje
   const Span out[2] = {{link_ab, (size_t)n * ka * OT_NLINK * sizeof(int)}, {link_ba, (size_t)n * kb * OT_NLINK * sizeof(int)}};
   const Span in[3] = {{votes, (size_t)n * ka * kb * sizeof(int)}, {objects_a, (size_t)n * ka * OT_NREC * sizeof(long long)},
                       {objects_b, (size_t)n * kb * OT_NREC * sizeof(long long)}};
-  if (any_overlap(out, in)) return FOTG_ERR_ARG;
+  if (overlap_any(out, in) || overlap_among(out)) return FOTG_ERR_ARG;
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   objlink_kernel<<<dim3((unsigned)n), OT_THREADS, 0, (hipStream_t)stream_>>>(votes, objects_a, objects_b, ka, kb, min_votes, min_frac256,
@@ -127,7 +83,7 @@ int fotg_object_tracks(int device, int T, int K, const long long *objects, const
                        {stats, OT_NSTAT * sizeof(long long)}};
   const Span in[3] = {{objects, (size_t)(T + 1) * K * OT_NREC * sizeof(long long)}, {link_ab, (size_t)T * K * OT_NLINK * sizeof(int)},
                       {link_ba, (size_t)T * K * OT_NLINK * sizeof(int)}};
-  if (any_overlap(out, in)) return FOTG_ERR_ARG;
+  if (overlap_any(out, in) || overlap_among(out)) return FOTG_ERR_ARG;
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   hipStream_t stream = (hipStream_t)stream_;

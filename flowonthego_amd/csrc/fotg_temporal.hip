@@ -5,33 +5,12 @@
 // on the caller's stream; the host arrays are consumed before the call returns.
 #include <cmath>
 #include <vector>
-#include "common.h"
+#include "host_call.h"
 #include "temporal.hip.h"
 
 using namespace fotg;
 
 namespace {
-
-struct DevGuard {                    // run on `dev`, leave the caller's current device as it was
-  int prev = -1;
-  bool ok = false;
-  hipError_t err = hipSuccess;       // what the failing hipGetDevice / hipSetDevice returned
-  explicit DevGuard(int dev)
-  {
-    int cur = -1;
-    if ((err = hipGetDevice(&cur)) != hipSuccess) return;
-    if (cur == dev) { ok = true; return; }
-    if ((err = hipSetDevice(dev)) != hipSuccess) return;
-    prev = cur; ok = true;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int hip_fail(hipError_t e)
-{
-  set_last_hip_error((int)e);
-  return FOTG_ERR_HIP;
-}
 
 template <class Src, class T>
 int temporal_batch(int device, int n, int K, int nframes, const Src &flow, const T *frames, int w, int h, int channels,
@@ -60,24 +39,20 @@ int temporal_batch(int device, int n, int K, int nframes, const Src &flow, const
   const long tiles_x = ((long)w + TEMPORAL_TW - 1) / TEMPORAL_TW, tiles_y = ((long)h + TEMPORAL_TH - 1) / TEMPORAL_TH;
   const long blocks = tiles_x * tiles_y;
   if (blocks > 0x7fffffffL || tiles_y > 65535 || n > 65535) return FOTG_ERR_ARG;
-  if (dst) {                         // the taps of a frame are read after pixels of dst have been written: no filtering in place
-    const char *a = reinterpret_cast<const char *>(frames), *b = reinterpret_cast<const char *>(dst);
-    const size_t abytes = (size_t)nframes * hw * channels * sizeof(T), bbytes = (size_t)n * hw * channels * sizeof(T);
-    if (a < b + bbytes && b < a + abytes) return FOTG_ERR_ARG;
-  }
+  // the taps of a frame are read after pixels of dst have been written: no filtering in place
+  const size_t img = (size_t)hw * channels * sizeof(T);
+  if (overlap(Span{frames, nframes * img}, Span{dst, n * img})) return FOTG_ERR_ARG;
   const float scale = 1.0f / (tau * (float)(9 * channels));
   DevGuard guard(device);
   if (!guard.ok) return hip_fail(guard.err);
   hipStream_t stream = (hipStream_t)stream_;
   int *dix = nullptr;
   WarpPartial *part = nullptr;
-  hipError_t e = hipMallocAsync((void **)&dix, ix.size() * sizeof(int), stream);
-  if (e != hipSuccess) return hip_fail(e);
-  if (stats) {
-    e = hipMallocAsync((void **)&part, (size_t)n * blocks * sizeof(WarpPartial), stream);
-    if (e != hipSuccess) { (void)hipFreeAsync(dix, stream); return hip_fail(e); }
-  }
-  e = hipMemcpyAsync(dix, ix.data(), ix.size() * sizeof(int), hipMemcpyHostToDevice, stream);   // pageable: consumed on return
+  Scratch mem(stream);
+  mem.get(&dix, ix.size() * sizeof(int));
+  if (stats) mem.get(&part, (size_t)n * blocks * sizeof(WarpPartial));
+  if (mem.err != hipSuccess) return mem.finish(mem.err);
+  hipError_t e = hipMemcpyAsync(dix, ix.data(), ix.size() * sizeof(int), hipMemcpyHostToDevice, stream);   // pageable: consumed on return
   if (e == hipSuccess) {
     const dim3 grid((unsigned)tiles_x, (unsigned)tiles_y, (unsigned)n);
     if (channels == 1)
@@ -90,10 +65,7 @@ int temporal_batch(int device, int n, int K, int nframes, const Src &flow, const
     temporal_fold_kernel<<<dim3((unsigned)n), WARP_THREADS, 0, stream>>>(part, (int)blocks, stats);
     e = hipGetLastError();
   }
-  if (part) { const hipError_t ef = hipFreeAsync(part, stream); if (e == hipSuccess) e = ef; }
-  const hipError_t ef = hipFreeAsync(dix, stream);
-  if (e == hipSuccess) e = ef;
-  return e == hipSuccess ? FOTG_OK : hip_fail(e);
+  return mem.finish(e);
 }
 
 template <class T>
@@ -104,9 +76,8 @@ int temporal_fused(fotg_ctx *ctx, int n, int K, int nframes, const float *flows,
   CtxUpsampleGeom g;
   if (!ctx || !flows || ctx_upsample_geom(ctx, &g) != FOTG_OK) return FOTG_ERR_ARG;
   if (n < 1 || K < 1 || K > TEMPORAL_MAXK || (long)n * K > g.max_batch || g.nch != 2) return FOTG_ERR_ARG;
-  const UpsampleSrc f{flows, (long)g.wl * g.hl * 2, g.wl, g.hl, g.sc_l, g.x0, g.y0};
-  return temporal_batch(g.device, n, K, nframes, f, frames, g.w_org, g.h_org, channels, center, neighbors, masks, tau, gains, ref,
-                        dst, used, stats, stream);
+  return temporal_batch(g.device, n, K, nframes, upsample_src(g, flows), frames, g.w_org, g.h_org, channels, center, neighbors, masks,
+                        tau, gains, ref, dst, used, stats, stream);
 }
 
 }  // namespace

@@ -12,7 +12,8 @@ black).  Prints the shares of the three codes and the mean change of a filtered 
 The module is callable: flowonthego_amd.filter_flow(flow, guide, ...) is flowonthego_amd.flowfilter.filter_flow(flow, guide, ...)."""
 import argparse
 import sys
-import types
+
+from ._lib import callable_module
 
 CODE_RGB = ((255, 255, 255), (220, 30, 30), (128, 128, 128), (0, 0, 0))
 
@@ -72,14 +73,7 @@ def main(argv=None):
     return 0
 
 
-class _Callable(types.ModuleType):
-    """importing this submodule binds the package attribute `filter_flow` to the module: calling it calls flowfilter.filter_flow()"""
-    def __call__(self, *a, **kw):
-        from .flowfilter import filter_flow
-        return filter_flow(*a, **kw)
-
-
-sys.modules[__name__].__class__ = _Callable
+callable_module(__name__, __package__ + ".flowfilter", "filter_flow")
 
 if __name__ == "__main__":
     sys.exit(main())

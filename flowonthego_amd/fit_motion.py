@@ -10,8 +10,9 @@ The module is callable: flowonthego_amd.fit_motion(flow, ...) is flowonthego_amd
 import argparse
 import struct
 import sys
-import types
 import zlib
+
+from ._lib import callable_module
 
 CODE_RGB = ((255, 255, 255), (220, 30, 30), (128, 128, 128), (0, 0, 0))
 
@@ -104,14 +105,7 @@ def main(argv=None):
     return 0
 
 
-class _Callable(types.ModuleType):
-    """importing this submodule binds the package attribute `fit_motion` to the module: calling it calls motion.fit_motion()"""
-    def __call__(self, *a, **kw):
-        from .motion import fit_motion
-        return fit_motion(*a, **kw)
-
-
-sys.modules[__name__].__class__ = _Callable
+callable_module(__name__, __package__ + ".motion", "fit_motion")
 
 if __name__ == "__main__":
     sys.exit(main())

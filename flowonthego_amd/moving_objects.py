@@ -10,8 +10,9 @@ xmin ymin xmax ymax  area  centroid x y  mean motion u v (pixels, relative to th
 The module is callable: flowonthego_amd.moving_objects(flow, ...) is flowonthego_amd.objects.moving_objects(flow, ...)."""
 import argparse
 import sys
-import types
 import zlib
+
+from ._lib import callable_module
 
 
 def main(argv=None):
@@ -66,14 +67,7 @@ def main(argv=None):
     return 0
 
 
-class _Callable(types.ModuleType):
-    """importing this submodule binds the package attribute `moving_objects` to the module: calling it calls objects.moving_objects()"""
-    def __call__(self, *a, **kw):
-        from .objects import moving_objects
-        return moving_objects(*a, **kw)
-
-
-sys.modules[__name__].__class__ = _Callable
+callable_module(__name__, __package__ + ".objects", "moving_objects")
 
 if __name__ == "__main__":
     sys.exit(main())

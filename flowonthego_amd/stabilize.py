@@ -10,7 +10,8 @@ Prints the share of such pixels per frame.
 The module is callable: flowonthego_amd.stabilize(frames, flows, ...) is flowonthego_amd.motion.stabilize(frames, flows, ...)."""
 import argparse
 import sys
-import types
+
+from ._lib import callable_module
 
 
 def main(argv=None):
@@ -55,14 +56,7 @@ def main(argv=None):
     return 0
 
 
-class _Callable(types.ModuleType):
-    """importing this submodule binds the package attribute `stabilize` to the module: calling it calls motion.stabilize()"""
-    def __call__(self, *a, **kw):
-        from .motion import stabilize
-        return stabilize(*a, **kw)
-
-
-sys.modules[__name__].__class__ = _Callable
+callable_module(__name__, __package__ + ".motion", "stabilize")
 
 if __name__ == "__main__":
     sys.exit(main())

@@ -7,12 +7,10 @@ no CPU fallback.
 
 The module is callable: flowonthego_amd.temporal(frames, ...) is flowonthego_amd.temporal.temporal_filter(frames, ...)."""
 import ctypes as C
-import sys
-import types
 
 import torch
 
-from ._lib import FotgError, check, lib
+from ._lib import FotgError, callable_module, check, lib
 from .oflow import _dev_f32, _ptr, _stream
 
 STATS = ("sum_used", "unfiltered", "sum_abs_filtered", "sum_abs_center")
@@ -175,10 +173,4 @@ def ofc_temporal_filter(ofc, frames, radius=1, tau=30.0, gains=None, occlusion=F
     return tuple(torch.cat([o[j] for o in outs]) for j in range(3))
 
 
-class _Callable(types.ModuleType):
-    """calling the module calls temporal_filter()"""
-    def __call__(self, *a, **kw):
-        return temporal_filter(*a, **kw)
-
-
-sys.modules[__name__].__class__ = _Callable
+callable_module(__name__, __name__, "temporal_filter")

@@ -12,7 +12,8 @@ id  frames first .. last  rows first last  mean area  largest area  votes  how i
 The module is callable: flowonthego_amd.track_objects(ids, objects, flows, ...) is flowonthego_amd.tracks.track_objects(...)."""
 import argparse
 import sys
-import types
+
+from ._lib import callable_module
 
 
 def main(argv=None):
@@ -78,14 +79,7 @@ def main(argv=None):
     return 0
 
 
-class _Callable(types.ModuleType):
-    """importing this submodule binds the package attribute `track_objects` to the module: calling it calls tracks.track_objects()"""
-    def __call__(self, *a, **kw):
-        from .tracks import track_objects
-        return track_objects(*a, **kw)
-
-
-sys.modules[__name__].__class__ = _Callable
+callable_module(__name__, __package__ + ".tracks", "track_objects")
 
 if __name__ == "__main__":
     sys.exit(main())

@@ -5,12 +5,10 @@ definition, in f32 and in order, is in include/fotg.h and csrc/warp.hip.h.  The 
 
 The module is callable: flowonthego_amd.warp(src, flow, ...) is flowonthego_amd.warp.warp(src, flow, ...)."""
 import ctypes as C
-import sys
-import types
 
 import torch
 
-from ._lib import FotgError, check, lib
+from ._lib import FotgError, callable_module, check, lib
 from .oflow import _dev_f32, _ptr, _stream
 
 STATS = ("valid", "occluded", "outside", "unknown", "sum_abs_warped", "sum_abs_unwarped")
@@ -96,10 +94,4 @@ def upsample_crop_warp(ofc, flow, src, ref=None, occ=None, fill=None, stats=Fals
     return _result(dst, cd, st, False, stats)
 
 
-class _Callable(types.ModuleType):
-    """importing this submodule binds the package attribute `warp` to the module: calling it calls warp()"""
-    def __call__(self, *a, **kw):
-        return warp(*a, **kw)
-
-
-sys.modules[__name__].__class__ = _Callable
+callable_module(__name__, __name__, "warp")

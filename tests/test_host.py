@@ -88,6 +88,22 @@ def test_only_tests_smoke_and_bench_touch_the_oracle():
             assert line.startswith("    "), line                               # only inside functions (cpu_baseline, the parity leg)
 
 
+def test_host_scaffold_exists_once():
+    """the host scaffold of the C-ABI files lives in csrc/host_call.h and the callable-module class in _lib.py: a new add-on
+    includes / calls them instead of pasting its own copy"""
+    pkg = os.path.join(ROOT, "flowonthego_amd")
+    for f in sorted(os.listdir(os.path.join(pkg, "csrc"))):
+        if f != "host_call.h":
+            txt = open(os.path.join(pkg, "csrc", f)).read()
+            assert "struct DevGuard" not in txt and not re.search(r"\bint\s+hip_fail\s*\(", txt), f
+    assert "struct DevGuard" in open(os.path.join(pkg, "csrc", "host_call.h")).read()
+    for dp, _, fs in os.walk(pkg):
+        for f in fs:
+            if f.endswith(".py") and f != "_lib.py":
+                assert not re.search(r"class\s+\w+\s*\([^)]*ModuleType", open(os.path.join(dp, f)).read()), f
+    assert "(types.ModuleType)" in open(os.path.join(pkg, "_lib.py")).read()
+
+
 def test_flo_writer_matches_reference_file_layout(tmp_path, alley_golden_flow):
     """write_flo == SaveFlowFile (kroeger/run_dense.cpp:16-57): tag, int32 w, int32 h, h*w*2 float32; the golden flow of the
     reference's own kroeger/flows/alley_0001.flo (tests/golden/alley_0001_flo.npz) survives a round trip bit for bit"""
