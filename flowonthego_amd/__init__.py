@@ -50,8 +50,12 @@ def __getattr__(name):
     if name in ("object_overlap", "upsample_crop_object_overlap", "object_links", "link_tracks", "TRACK", "TRACK_STATS"):
         from . import tracks
         return getattr(tracks, name)
-    if name in ("fit_motion", "stabilize", "moving_objects", "track_objects"):
-        # (the command-line modules of these names; each is callable as the function of flowonthego_amd.motion / objects / tracks)
+    if name in ("upsample_crop_motion_histograms", "motion_descriptors", "HIST"):
+        from . import histograms
+        return getattr(histograms, name)
+    if name in ("fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms"):
+        # (the command-line modules of these names; each is callable as the function of flowonthego_amd.motion / objects / tracks /
+        # histograms)
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("interpolate", "upsample_crop_interpolate"):

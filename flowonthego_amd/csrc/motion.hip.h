@@ -52,37 +52,12 @@
 #include "common.h"
 #include "flowsrc.hip.h"
 #include "warp.hip.h"
+#include "motion_model.hip.h"
 
 namespace fotg {
 
 enum { MOTION_THREADS = 256, MOTION_NSUM = 12, MOTION_NSTAT = 6, MOTION_MAX_DIM = 16384, MOTION_MAX_ITERS = 64 };
 enum { MOTION_ROUND0 = 0, MOTION_ROUND = 1, MOTION_FINAL = 2 };
-
-struct MotionCoef { float k[6]; };
-
-// the f32 coefficients of the prediction in the centred frame from the six pixel-frame parameters P
-__host__ __device__ inline MotionCoef motion_coef(const double *P, int w, int h)
-{
-  const double wx = (double)(w - 1), hy = (double)(h - 1);
-  MotionCoef m;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const double h0 = P[3 * r] * 0.5, h1 = P[3 * r + 1] * 0.5;
-    m.k[3 * r] = (float)h0;
-    m.k[3 * r + 1] = (float)h1;
-    m.k[3 * r + 2] = (float)((P[3 * r + 2] + h0 * wx) + h1 * hy);
-  }
-  return m;
-}
-
-__host__ __device__ inline void motion_predict(const MotionCoef &m, int X, int Y, float &pu, float &pv)
-{
-  const float Xf = (float)X, Yf = (float)Y;
-  pu = (m.k[0] * Xf + m.k[1] * Yf) + m.k[2];
-  pv = (m.k[3] * Xf + m.k[4] * Yf) + m.k[5];
-}
-
-__host__ __device__ inline bool motion_known(float u, float v) { return fabsf(u) <= 4096.f && fabsf(v) <= 4096.f; }
 
 // the solve of the head of this file: false (c untouched) where the system is unusable
 __host__ __device__ inline bool motion_solve(const long long (&S)[MOTION_NSUM], int model, double (&c)[6])

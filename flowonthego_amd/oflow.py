@@ -355,6 +355,23 @@ class OFClass:
                                  connectivity=connectivity, min_votes=min_votes, min_frac=min_frac, max_tracks=max_tracks,
                                  track_ids=track_ids, stats=stats)
 
+    def upsample_crop_motion_histograms(self, flow, mask=None, motion=None, cell=16, thresh=0.4, ids=None, rows=256, cells=True, fused=True):
+        """HOF and MBH per cell and/or per object of upsample_crop(flow): int64 records of 32 columns; fused: the full-resolution flow
+        is never written -- flowonthego_amd.histograms"""
+        from .histograms import upsample_crop_motion_histograms
+        return upsample_crop_motion_histograms(self, flow, mask=mask, motion=motion, cell=cell, thresh=thresh, ids=ids, rows=rows,
+                                               cells=cells, fused=fused)
+
+    def motion_histograms(self, frames, cell=16, model="affine", occlusion=False, objects=False, thresh=0.4, iters=3, fit_thresh=1.0,
+                          min_area=64, max_objects=256, connectivity=8, cells=True):
+        """the flows of frames (T+1, ...), the camera motion of each (model=None: none), with occlusion the consistency mask, with
+        objects the ids of moving_objects, then the fused histograms: (params, cells[, object histograms, objects, ids]) --
+        flowonthego_amd.histograms"""
+        from .histograms import ofc_motion_histograms
+        return ofc_motion_histograms(self, frames, cell=cell, model=model, occlusion=occlusion, objects=objects, thresh=thresh, iters=iters,
+                                     fit_thresh=fit_thresh, min_area=min_area, max_objects=max_objects, connectivity=connectivity,
+                                     cells=cells)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

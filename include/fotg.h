@@ -742,6 +742,48 @@ int fotg_object_links(int device, int n, const int *votes, const long long *obje
 int fotg_object_tracks(int device, int T, int K, const long long *objects, const int *link_ab, const int *link_ba, int max_tracks,
                        int *track, long long *tracks, long long *stats, void *stream);
 
+/* ---- motion histograms: HOF and MBH per cell and per object, csrc/histograms.hip.h ------------------------------------------------
+ * What turns a flow into features: the histogram of optical flow (HOF) and the motion-boundary histograms (MBHx, MBHy) of the
+ * dense-trajectories family, per cell of a regular grid and/or per object of an `ids` map (fotg_label_components).  Integer
+ * arithmetic after the first step: every sum is an integer sum, the same bytes in any order of accumulation.  Inputs: flow,
+ * n x h x w x 2 f32; mask, NULL or n x h x w uint8 in the alphabet of fotg_fb_check; params, NULL or n x 6 f64, the pixel-frame
+ * parameters fotg_fit_motion returns (the camera motion to subtract); ids, NULL or int32 n x h x w.  The definition, in order:
+ *   1. Residual.  (u, v) must be known: |u| <= 4096 and |v| <= 4096 (false for a NaN or an infinity).  With params, (pu, pv) is the
+ *      model's vector at the pixel exactly as fotg_motion_flow writes it, ru = u - pu, rv = v - pv (one f32 subtraction each), and
+ *      (ru, rv) must be known again; without, ru = u, rv = v.
+ *   2. A pixel is admissible iff step 1 passes and (mask == NULL or its mask byte is 0).  U = (int)rintf(256 ru), V = (int)rintf(256 rv).
+ *   3. M(a, b) = floor(sqrt(a a + b b)), the exact integer square root of the 64-bit sum.
+ *   4. The angle index A(a, b) in [0, 2048), in units of 45/256 degrees, for (a, b) != (0, 0).  With ax = |a|, ay = |b|:
+ *      phi = T[(ay << 8) / ax] if ax >= ay, else 512 - T[(ax << 8) / ay] (integer division), and by the signs
+ *      a >= 0, b >= 0: A = phi;  a < 0, b >= 0: A = 1024 - phi;  a < 0, b < 0: A = 1024 + phi;  a >= 0, b < 0: A = (2048 - phi) mod 2048.
+ *      T[k] = rint(256 atan(k / 256) / (pi / 4)) for k = 0 .. 256, a literal table (MH_ATAN of csrc/histograms.hip.h).
+ *   5. Soft binning of a weight m at angle A: b0 = A >> 8, f = A & 255, w1 = (m f) >> 8, w0 = m - w1; w0 goes to bin b0, w1 to bin
+ *      (b0 + 1) & 7: eight bins centred on the multiples of 45 degrees, linear interpolation between neighbours.
+ *   6. HOF, for an admissible pixel with m = M(U, V): m < thresh256 counts one in the zero-bin column and adds no orientation weight;
+ *      otherwise m is soft-binned at A(U, V).  thresh256 = 0 sends nothing to the zero bin; a pixel with U = V = 0 then adds nothing.
+ *   7. MBH.  Ux = U[y][min(x+1, w-1)] - U[y][max(x-1, 0)], Uy = U[min(y+1, h-1)][x] - U[max(y-1, 0)][x], Vx and Vy alike: clamped
+ *      coordinates, so the difference is one-sided at the border.  A pixel takes part iff it and its four clamped neighbours are
+ *      admissible.  MBHx soft-bins M(Ux, Uy) at A(Ux, Uy), MBHy M(Vx, Vy) at A(Vx, Vy); a zero gradient counts and adds nothing.
+ *   8. The record, 32 int64: [0..7] HOF bins, [8] zero-bin pixels, [9..16] MBHx bins, [17..24] MBHy bins, [25] admissible pixels,
+ *      [26] pixels in MBH, [27] pixels of the cell or object that are not admissible, [28] the sum of m, [29] of U, [30] of V over the
+ *      admissible pixels, [31] 0.
+ *   9. cells (may be NULL), int64 n x ceil(h / cell) x ceil(w / cell) x 32, cell in {8, 16, 32}; edge cells are partial.  objects (may be
+ *      NULL; needs ids), int64 n x rows x 32: a pixel with i = ids[y][x] in [0, rows) adds to row i, every other id, -1 included, is
+ *      background; a pixel's MBH goes to its own row whatever its neighbours' ids are.  Both are complete after the call, zero rows
+ *      included.
+ * Two identical calls give identical bytes; there are no floating-point atomics.  Everything is enqueued on `stream`.  FOTG_ERR_ARG,
+ * decided before anything is launched or cleared: n < 1 (or > 65535), w or h outside 1 .. 16384, a null flow, cell not 8, 16 or 32,
+ * thresh256 < 0, cells and objects both NULL, objects without ids, rows outside 1 .. 1024 (read only with objects), an output
+ * overlapping an input or the other output. */
+int fotg_motion_histograms(int device, int n, const float *flow, int w, int h, const unsigned char *mask, const double *params, int cell,
+                           int thresh256, long long *cells, const int *ids, int rows, long long *objects, void *stream);
+/* The same on the coarse flow of a context (n x hl x wl x 2, as fotg_calc_batch returns it), upsampled and cropped on the fly, mask and
+ * ids of h_org x w_org: both outputs equal fotg_motion_histograms on fotg_upsample_crop's output bit for bit, without the
+ * full-resolution flow ever being written.  FOTG_ERR_ARG also for n > max_batch and a depth-mode context. */
+int fotg_upsample_crop_motion_histograms(fotg_ctx *ctx, int n, const float *coarse_flow, const unsigned char *mask, const double *params,
+                                         int cell, int thresh256, long long *cells, const int *ids, int rows, long long *objects,
+                                         void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
