@@ -6,8 +6,8 @@ to it.  All arithmetic is integer; the definition is in include/fotg.h and csrc/
 CPU fallback."""
 import torch
 
+from ._args import _dev_f32, _ptr, _stream, batched, cat_chunks, coarse_flow, coarse_shape, dense_flow, image_stack, optional, two_channel, unbatch
 from ._lib import FotgError, check, lib
-from .oflow import _dev_f32, _ptr, _stream
 
 KINDS = ("zero", "mean", "centre", "top_left", "top_right", "bottom_left", "bottom_right")
 MOVED = 8
@@ -23,27 +23,13 @@ def _check_params(block, refine):
 
 
 def _frames(cur, ref, n, h, w, device, single):
-    """the frames checked: (cur, ref as (n, h, w[, c]), channels)"""
-    for t, nm in ((cur, "cur"), (ref, "ref")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-            raise FotgError("%s must be a uint8 tensor (the arithmetic is integer)" % nm)
-    if single:
-        cur, ref = cur.unsqueeze(0), ref.unsqueeze(0)
-    if cur.dim() not in (3, 4):
-        raise FotgError("cur has shape %s, expected (n, h, w) or (n, h, w, 1 | 3)" % (tuple(cur.shape),))
-    ch = 1 if cur.dim() == 3 else int(cur.shape[3])
-    if ch not in (1, 3):
-        raise FotgError("cur has %d channels, expected 1 or 3" % ch)
-    shape = (n, h, w) + tuple(cur.shape[3:])
-    _dev_f32(cur, "cur", device, shape, dtype=torch.uint8)
-    _dev_f32(ref, "ref", device, shape, dtype=torch.uint8)
-    return cur, ref, ch
+    """the frames checked: (cur, ref as (n, h, w[, c]), channels); uint8, the arithmetic is integer"""
+    cur, ch = image_stack(cur, "cur", n, h, w, device, (torch.uint8,), single)
+    return cur, _dev_f32(batched(ref, single), "ref", device, cur.shape, torch.uint8), ch
 
 
 def _outputs(n, h, w, block, cur, device, mask, pred, stats, single):
-    if mask is not None:
-        mask = mask.unsqueeze(0) if single and isinstance(mask, torch.Tensor) else mask
-        _dev_f32(mask, "mask", device, (n, h, w), dtype=torch.uint8)
+    mask = optional(mask, "mask", device, (n, h, w), torch.uint8, single)
     bw, bh = -(-w // block), -(-h // block)
     mv = torch.empty((n, bh, bw, 2), dtype=torch.int16, device=device)
     cost = torch.empty((n, bh, bw, 2), dtype=torch.int32, device=device)           # returned as uint32
@@ -51,11 +37,6 @@ def _outputs(n, h, w, block, cur, device, mask, pred, stats, single):
     pr = torch.empty_like(cur) if pred else None
     st = torch.empty((n, len(STATS)), dtype=torch.int64, device=device) if stats else None
     return mask, mv, cost, kind, pr, st
-
-
-def _result(mv, cost, kind, pr, st, single):
-    r = (mv, cost.view(torch.uint32), kind) + ((pr,) if pr is not None else ()) + ((st,) if st is not None else ())
-    return tuple(t[0] for t in r) if single else r
 
 
 def block_motion(cur, ref, flow, mask=None, block=16, refine=2, pred=False, stats=False):
@@ -66,48 +47,30 @@ def block_motion(cur, ref, flow, mask=None, block=16, refine=2, pred=False, stat
     vector], kind uint8 (n, bh, bw) = the winning candidate (KINDS) | 8 (MOVED) if a refinement step moved it; with pred=True also
     the prediction, uint8 shaped like cur; with stats=True also int64 (n, 11) (STATS).  A single image returns everything without
     the batch dimension.  Asynchronous on the current stream."""
-    if not isinstance(flow, torch.Tensor) or flow.dim() not in (3, 4) or flow.shape[-1] != 2:
-        raise FotgError("flow must be a (n, h, w, 2) or (h, w, 2) tensor")
     _check_params(block, refine)
-    single = flow.dim() == 3
-    f = flow.unsqueeze(0) if single else flow
-    n, h, w = (int(v) for v in f.shape[:3])
-    if n < 1 or h < 1 or w < 1:
-        raise FotgError("flow has an empty dimension: %s" % (tuple(flow.shape),))
-    _dev_f32(f, "flow")
+    f, single, n, h, w = dense_flow(flow)
     c, r, ch = _frames(cur, ref, n, h, w, f.device, single)
     mask, mv, cost, kind, pr, st = _outputs(n, h, w, block, c, f.device, mask, pred, stats, single)
     check(lib().fotg_block_motion(f.device.index or 0, n, _ptr(c), _ptr(r), w, h, ch, _ptr(f), _ptr(mask), block, refine, _ptr(mv),
                                   _ptr(cost), _ptr(kind), _ptr(pr), _ptr(st), _stream(f.device)))
-    return _result(mv, cost, kind, pr, st, single)
+    return unbatch((mv, cost.view(torch.uint32), kind, pr, st), single)
 
 
 def upsample_crop_block_motion(ofc, coarse, cur, ref, mask=None, block=16, refine=2, pred=False, stats=False, fused=True):
     """The context's coarse flow (n, h_l, w_l, 2) and the frames (n, h_org, w_org[, c]) -> bit for bit
     block_motion(cur, ref, ofc.upsample_crop(coarse), ...).  fused=True evaluates the upsampling inside the kernel and never writes
     the full-resolution flow; fused=False runs upsample_crop and the dense form."""
-    if ofc.nch != 2:
-        raise FotgError("block motion needs a two-channel flow (this is a depth-mode context)")
-    n = coarse.shape[0] if isinstance(coarse, torch.Tensor) and coarse.dim() == 4 else 0
-    if n < 1 or n > ofc.max_batch:
-        raise FotgError("coarse must be (n, h_l, w_l, 2) with 1 <= n <= max_batch")
+    n = coarse_flow(ofc, coarse, "block motion needs a two-channel flow")
     if not fused:
         return block_motion(cur, ref, ofc.upsample_crop(coarse), mask=mask, block=block, refine=refine, pred=pred, stats=stats)
     _check_params(block, refine)
-    wl, hl = ofc.out_size()
-    _dev_f32(coarse, "coarse", ofc.device, (n, hl, wl, 2))
+    coarse_shape(ofc, coarse, "coarse", n)
     h, w = ofc.height_org, ofc.width_org
     c, r, ch = _frames(cur, ref, n, h, w, ofc.device, False)
     mask, mv, cost, kind, pr, st = _outputs(n, h, w, block, c, ofc.device, mask, pred, stats, False)
     check(lib().fotg_upsample_crop_block_motion(ofc._h, n, _ptr(coarse), _ptr(c), _ptr(r), ch, _ptr(mask), block, refine, _ptr(mv),
                                                 _ptr(cost), _ptr(kind), _ptr(pr), _ptr(st), _stream(ofc.device)))
-    return _result(mv, cost, kind, pr, st, False)
-
-
-def _cat(ts):
-    if ts[0].dtype == torch.uint32:
-        return torch.cat([t.view(torch.int32) for t in ts]).view(torch.uint32)
-    return torch.cat(ts)
+    return unbatch((mv, cost.view(torch.uint32), kind, pr, st), False)
 
 
 def ofc_block_motion(ofc, I0, I1, block=16, refine=2, occlusion=False, pred=False, stats=False):
@@ -115,8 +78,7 @@ def ofc_block_motion(ofc, I0, I1, block=16, refine=2, occlusion=False, pred=Fals
     max_batch pairs per chunk, the full-resolution flow never written.  occlusion=True (a bidir context): both directions are
     computed and only the vectors upsample_crop_fb_check accepts propose candidates.  Returns (flow, mv, cost, kind[, pred][,
     stats]), flow the coarse flow as calc_batch_u8 returns it."""
-    if ofc.nch != 2:
-        raise FotgError("block motion needs a two-channel flow (this is a depth-mode context)")
+    two_channel(ofc, "block motion needs a two-channel flow")
     if occlusion and not ofc.op.bidir:
         raise FotgError("block_motion(occlusion=True) needs a context created with opt_params.bidir = True")
     if not isinstance(I0, torch.Tensor) or not isinstance(I1, torch.Tensor) or I0.shape != I1.shape or I0.dim() < 3:
@@ -134,4 +96,4 @@ def ofc_block_motion(ofc, I0, I1, block=16, refine=2, occlusion=False, pred=Fals
         else:
             fw = ofc.calc_batch_u8(a, b)
         parts.append((fw,) + upsample_crop_block_motion(ofc, fw, a, b, mask=m, block=block, refine=refine, pred=pred, stats=stats))
-    return parts[0] if len(parts) == 1 else tuple(_cat([p[j] for p in parts]) for j in range(len(parts[0])))
+    return cat_chunks(parts)

@@ -9,8 +9,8 @@ import ctypes as C
 
 import torch
 
+from ._args import _dev_f32, _ptr, _stream, coarse_flow, coarse_shape, optional, unbatch
 from ._lib import FotgError, callable_module, check, lib
-from .oflow import _dev_f32, _ptr, _stream
 
 STATS = ("valid", "occluded", "outside", "unknown", "sum_steps")
 
@@ -23,13 +23,10 @@ def _sequences(flows, flows_bw):
     if flows_bw is not None and (not isinstance(flows_bw, torch.Tensor) or flows_bw.shape != flows.shape):
         raise FotgError("flows_bw must have the shape of flows, %s" % (tuple(flows.shape),))
     f = flows.unsqueeze(0) if single else flows
-    b = None if flows_bw is None else (flows_bw.unsqueeze(0) if single else flows_bw)
     if min(int(v) for v in f.shape) < 1:
         raise FotgError("flows has an empty dimension: %s" % (tuple(flows.shape),))
     _dev_f32(f, "flows")
-    if b is not None:
-        _dev_f32(b, "flows_bw", f.device)
-    return f, b, single
+    return f, optional(flows_bw, "flows_bw", f.device, f.shape, single=single), single
 
 
 def _points(points, n_seq, device):
@@ -57,11 +54,6 @@ def _points_out(n_seq, T, P, device, stats):
     return traj, code, steps, st
 
 
-def _result(outs, single, stats):
-    outs = outs if stats else outs[:3]
-    return tuple(o[0] for o in outs) if single else tuple(outs)
-
-
 def chain(flows, flows_bw=None, alpha1=0.01, alpha2=0.5, stats=False):
     """flows: device tensor (T, h, w, 2) or (n_seq, T, h, w, 2) float32, flows[k] the flow frame k -> k+1; flows_bw: None or alike,
     flows_bw[k] the flow frame k+1 -> k (then every step is tested for forward-backward consistency, alpha1 and alpha2 as in
@@ -75,7 +67,7 @@ def chain(flows, flows_bw=None, alpha1=0.01, alpha2=0.5, stats=False):
     outs = _dense_out(n_seq, h, w, f.device, stats)
     check(lib().fotg_flow_chain(f.device.index or 0, n_seq, T, _ptr(f), _ptr(b), w, h, C.c_float(alpha1), C.c_float(alpha2),
                                 *(_ptr(o) for o in outs), _stream(f.device)))
-    return _result(outs, single, stats)
+    return unbatch(outs, single, always_tuple=True)
 
 
 def track_points(points, flows, flows_bw=None, alpha1=0.01, alpha2=0.5, stats=False):
@@ -91,21 +83,16 @@ def track_points(points, flows, flows_bw=None, alpha1=0.01, alpha2=0.5, stats=Fa
     outs = _points_out(n_seq, T, P, f.device, stats)
     check(lib().fotg_track_points(f.device.index or 0, n_seq, T, _ptr(f), _ptr(b), w, h, C.c_float(alpha1), C.c_float(alpha2), P,
                                   _ptr(pts), *(_ptr(o) for o in outs), _stream(f.device)))
-    return _result(outs, single, stats)
+    return unbatch(outs, single, always_tuple=True)
 
 
 def _coarse(ofc, flows, flows_bw):
     """the context's coarse flows (T, h_l, w_l, 2) of one sequence checked: T"""
-    T = flows.shape[0] if isinstance(flows, torch.Tensor) and flows.dim() == 4 else 0
-    if ofc.nch != 2:
-        raise FotgError("the chain needs two-channel flows (this is a depth-mode context)")
-    if T < 1 or T > ofc.max_batch:
-        raise FotgError("flows must be (T, h_l, w_l, 2) with 1 <= T <= max_batch")
-    wl, hl = ofc.out_size()
-    _dev_f32(flows, "flows", ofc.device, (T, hl, wl, 2))
+    T = coarse_flow(ofc, flows, "the chain needs two-channel flows", "flows", "T")
+    coarse_shape(ofc, flows, "flows", T)
     if flows_bw is not None:
-        _dev_f32(flows_bw, "flows_bw", ofc.device, (T, hl, wl, 2))
-    return int(T)
+        coarse_shape(ofc, flows_bw, "flows_bw", T)
+    return T
 
 
 def upsample_crop_chain(ofc, flows, flows_bw=None, alpha1=0.01, alpha2=0.5, stats=False, fused=None):
@@ -122,7 +109,7 @@ def upsample_crop_chain(ofc, flows, flows_bw=None, alpha1=0.01, alpha2=0.5, stat
     outs = _dense_out(1, ofc.height_org, ofc.width_org, ofc.device, stats)
     check(lib().fotg_upsample_crop_flow_chain(ofc._h, T, _ptr(flows), _ptr(flows_bw), C.c_float(alpha1), C.c_float(alpha2),
                                               *(_ptr(o) for o in outs), _stream(ofc.device)))
-    return _result(outs, True, stats)
+    return unbatch(outs, True, always_tuple=True)
 
 
 def upsample_crop_track_points(ofc, points, flows, flows_bw=None, alpha1=0.01, alpha2=0.5, stats=False, fused=False):
@@ -140,7 +127,7 @@ def upsample_crop_track_points(ofc, points, flows, flows_bw=None, alpha1=0.01, a
     outs = _points_out(1, T, P, ofc.device, stats)
     check(lib().fotg_upsample_crop_track_points(ofc._h, T, _ptr(flows), _ptr(flows_bw), C.c_float(alpha1), C.c_float(alpha2), P, _ptr(pts),
                                                 *(_ptr(o) for o in outs), _stream(ofc.device)))
-    return _result(outs, True, stats)
+    return unbatch(outs, True, always_tuple=True)
 
 
 def track(ofc, frames, points=None, alpha1=0.01, alpha2=0.5, stats=False, fused=None):

@@ -8,8 +8,8 @@ import zlib
 import numpy as np
 import torch
 
-from ._lib import FotgError, check, lib
-from .oflow import _dev_f32, _ptr, _stream
+from ._args import _dev_f32, _ptr, _stream, coarse_flow, coarse_shape, dense_flow
+from ._lib import check, lib
 
 
 def _maxmotion(maxmotion):
@@ -27,14 +27,7 @@ def flow_to_color(flow, maxmotion=None, out=None, stats=False):
     maxmotion None (or <= 0): each image normalised by its own largest known |(u, v)|, as color_flow without its argument.
     stats=True also returns an (n, 5) float32 tensor: maxrad, minu, maxu, minv, maxv over the known vectors (what color_flow prints).
     Asynchronous on the current stream of the flow's device."""
-    if not isinstance(flow, torch.Tensor) or flow.dim() not in (3, 4) or flow.shape[-1] != 2:
-        raise FotgError("flow must be a (n, h, w, 2) or (h, w, 2) tensor")
-    single = flow.dim() == 3
-    f = flow.unsqueeze(0) if single else flow
-    n, h, w = (int(v) for v in f.shape[:3])
-    if n < 1 or h < 1 or w < 1:
-        raise FotgError("flow has an empty dimension: %s" % (tuple(flow.shape),))
-    _dev_f32(f, "flow")
+    f, single, n, h, w = dense_flow(flow)
     rgb = _out_rgb(out.unsqueeze(0) if (single and out is not None) else out, (n, h, w, 3), f.device)
     st = torch.empty((n, 5), dtype=torch.float32, device=f.device)
     check(lib().fotg_flow_color(f.device.index or 0, n, _ptr(f), w, h, _maxmotion(maxmotion), _ptr(rgb), _ptr(st), _stream(f.device)))
@@ -45,13 +38,8 @@ def flow_to_color(flow, maxmotion=None, out=None, stats=False):
 def upsample_crop_color(ofc, flow, maxmotion=None, out=None, stats=False):
     """OFClass.upsample_crop_color: the context's coarse flow (n, h_l, w_l, 2) -> uint8 (n, h_org, w_org, 3), byte for byte
     flow_to_color(ofc.upsample_crop(flow)) without the full-resolution flow ever being written."""
-    n = flow.shape[0] if isinstance(flow, torch.Tensor) and flow.dim() == 4 else 0
-    if ofc.nch != 2:
-        raise FotgError("the colour code needs a two-channel flow (this is a depth-mode context)")
-    if n < 1 or n > ofc.max_batch:
-        raise FotgError("flow must be (n, h_l, w_l, 2) with 1 <= n <= max_batch")
-    w, h = ofc.out_size()
-    _dev_f32(flow, "flow", ofc.device, (n, h, w, 2))
+    n = coarse_flow(ofc, flow, "the colour code needs a two-channel flow", "flow")
+    coarse_shape(ofc, flow, "flow", n)
     rgb = _out_rgb(out, (n, ofc.height_org, ofc.width_org, 3), ofc.device)
     st = torch.empty((n, 5), dtype=torch.float32, device=ofc.device)
     check(lib().fotg_upsample_crop_color(ofc._h, n, _ptr(flow), _maxmotion(maxmotion), _ptr(rgb), _ptr(st), _stream(ofc.device)))

@@ -6,8 +6,8 @@ import ctypes as C
 
 import torch
 
+from ._args import _ptr, _stream, coarse_flow, coarse_shape, dense_flow, flow_form, optional, unbatch
 from ._lib import FotgError, check, lib
-from .oflow import _dev_f32, _ptr, _stream
 
 CODES = ("consistent", "occluded", "outside", "unknown")
 
@@ -24,24 +24,16 @@ def fb_check(fw, bw, alpha1=0.01, alpha2=0.5, stats=False):
     Returns (mask, mask_bw) uint8 (n, h, w) or (h, w): mask over frame 0 (fw checked against bw), mask_bw over frame 1.
     stats=True also returns counts, int32 (n, 2, 4) or (2, 4): per direction the number of pixels of each code.
     Asynchronous on the current stream of the flows' device."""
-    for t, nm in ((fw, "fw"), (bw, "bw")):
-        if not isinstance(t, torch.Tensor) or t.dim() not in (3, 4) or t.shape[-1] != 2:
-            raise FotgError("%s must be a (n, h, w, 2) or (h, w, 2) tensor" % nm)
+    flow_form(fw, "fw")
+    flow_form(bw, "bw")
     if fw.shape != bw.shape:
         raise FotgError("fw and bw differ in shape: %s and %s" % (tuple(fw.shape), tuple(bw.shape)))
-    single = fw.dim() == 3
-    f, b = (fw.unsqueeze(0), bw.unsqueeze(0)) if single else (fw, bw)
-    n, h, w = (int(v) for v in f.shape[:3])
-    if n < 1 or h < 1 or w < 1:
-        raise FotgError("flow has an empty dimension: %s" % (tuple(fw.shape),))
-    _dev_f32(f, "fw")
-    _dev_f32(b, "bw", f.device)
+    f, single, n, h, w = dense_flow(fw, "fw")
+    b = optional(bw, "bw", f.device, f.shape, single=single)
     m, mb, cnt = _masks((n, h, w), f.device, stats)
     check(lib().fotg_fb_check(f.device.index or 0, n, _ptr(f), _ptr(b), w, h, C.c_float(alpha1), C.c_float(alpha2),
                               _ptr(m), _ptr(mb), _ptr(cnt), _stream(f.device)))
-    if single:
-        m, mb, cnt = m[0], mb[0], (cnt[0] if stats else None)
-    return (m, mb, cnt) if stats else (m, mb)
+    return unbatch((m, mb, cnt), single, always_tuple=True)
 
 
 def upsample_crop_fb_check(ofc, fw, bw, alpha1=0.01, alpha2=0.5, stats=False, fused=False):
@@ -49,20 +41,15 @@ def upsample_crop_fb_check(ofc, fw, bw, alpha1=0.01, alpha2=0.5, stats=False, fu
     fb_check(ofc.upsample_crop(fw), ofc.upsample_crop(bw)).  fused=False (the default: measured 8 % faster at 64 x 1080p,
     DESIGN.md section 11) runs the two upsample_crop calls and the dense check; fused=True evaluates the upsampling inside the
     check and never writes either full-resolution flow (2 x 1.06 GB less HBM at 64 x 1080p)."""
-    n = fw.shape[0] if isinstance(fw, torch.Tensor) and fw.dim() == 4 else 0
-    if ofc.nch != 2:
-        raise FotgError("the consistency check needs two-channel flows (this is a depth-mode context)")
-    if n < 1 or n > ofc.max_batch:
-        raise FotgError("flows must be (n, h_l, w_l, 2) with 1 <= n <= max_batch")
+    n = coarse_flow(ofc, fw, "the consistency check needs two-channel flows", "flows")
     if not fused:
         return fb_check(ofc.upsample_crop(fw), ofc.upsample_crop(bw), alpha1, alpha2, stats)
-    w, h = ofc.out_size()
-    _dev_f32(fw, "fw", ofc.device, (n, h, w, 2))
-    _dev_f32(bw, "bw", ofc.device, (n, h, w, 2))
+    coarse_shape(ofc, fw, "fw", n)
+    coarse_shape(ofc, bw, "bw", n)
     m, mb, cnt = _masks((n, ofc.height_org, ofc.width_org), ofc.device, stats)
     check(lib().fotg_upsample_crop_fb_check(ofc._h, n, _ptr(fw), _ptr(bw), C.c_float(alpha1), C.c_float(alpha2),
                                             _ptr(m), _ptr(mb), _ptr(cnt), _stream(ofc.device)))
-    return (m, mb, cnt) if stats else (m, mb)
+    return unbatch((m, mb, cnt), False, always_tuple=True)
 
 
 # palette of the mask image: code 0 white, 1 red, 2 blue, 3 black

@@ -9,8 +9,8 @@ import math
 
 import torch
 
+from ._args import _ptr, _stream, cat_chunks, coarse_flow, coarse_shape, dense_flow, image_stack, optional, two_channel, unbatch
 from ._lib import FotgError, check, lib
-from .oflow import _dev_f32, _ptr, _stream
 
 CODES = ("filtered", "filled", None, "unsupported")
 STATS = ("filtered", "filled", "unsupported", "sum_abs_change")
@@ -48,37 +48,13 @@ def _spatial(radius, sigma, spatial):
     return (C.c_float * len(s))(*s)
 
 
-def _guide(guide, n, h, w, device, single):
-    """the guide checked: (guide as (n, h, w[, c]), channels)"""
-    if not isinstance(guide, torch.Tensor) or guide.dtype not in (torch.float32, torch.uint8):
-        raise FotgError("guide must be a float32 or uint8 tensor")
-    if single:
-        guide = guide.unsqueeze(0)
-    if guide.dim() not in (3, 4):
-        raise FotgError("guide has shape %s, expected (n, h, w) or (n, h, w, 1 | 3)" % (tuple(guide.shape),))
-    ch = 1 if guide.dim() == 3 else int(guide.shape[3])
-    if ch not in (1, 3):
-        raise FotgError("guide has %d channels, expected 1 or 3" % ch)
-    _dev_f32(guide, "guide", device, (n, h, w) + tuple(guide.shape[3:]), dtype=guide.dtype)
-    return guide, ch
-
-
 def _outputs(n, h, w, device, mask, code, stats, single):
-    if mask is not None:
-        mask = mask.unsqueeze(0) if single and isinstance(mask, torch.Tensor) else mask
-        _dev_f32(mask, "mask", device, (n, h, w), dtype=torch.uint8)
+    mask = optional(mask, "mask", device, (n, h, w), torch.uint8, single)
     want_code = code is None and stats or bool(code)
     out = torch.empty((n, h, w, 2), dtype=torch.float32, device=device)
     cd = torch.empty((n, h, w), dtype=torch.uint8, device=device) if want_code else None
     st = torch.empty((n, 4), dtype=torch.float64, device=device) if stats else None
     return mask, out, cd, st
-
-
-def _result(out, cd, st, single):
-    if single:
-        out, cd, st = out[0], (None if cd is None else cd[0]), (None if st is None else st[0])
-    r = (out,) + ((cd,) if cd is not None else ()) + ((st,) if st is not None else ())
-    return r[0] if len(r) == 1 else r
 
 
 def filter_flow(flow, guide, mask=None, radius=3, sigma=None, spatial=None, tau=20.0, iters=1, code=None, stats=False):
@@ -91,21 +67,14 @@ def filter_flow(flow, guide, mask=None, radius=3, sigma=None, spatial=None, tau=
     Returns out, the filtered flow; with code=True (out, code), code uint8: 0 filtered, 1 filled from its neighbours, 3 no support;
     with stats=True (out, code, stats), stats float64 (n, 4) / (4,): the pixels of code 0, 1 and 3 and the sum of |change| over the
     components of the code-0 pixels (STATS); stats=True, code=False leaves the code out.  Asynchronous on the current stream."""
-    if not isinstance(flow, torch.Tensor) or flow.dim() not in (3, 4) or flow.shape[-1] != 2:
-        raise FotgError("flow must be a (n, h, w, 2) or (h, w, 2) tensor")
-    single = flow.dim() == 3
-    f = flow.unsqueeze(0) if single else flow
-    n, h, w = (int(v) for v in f.shape[:3])
-    if n < 1 or h < 1 or w < 1:
-        raise FotgError("flow has an empty dimension: %s" % (tuple(flow.shape),))
-    _dev_f32(f, "flow")
-    g, ch = _guide(guide, n, h, w, f.device, single)
+    f, single, n, h, w = dense_flow(flow)
+    g, ch = image_stack(guide, "guide", n, h, w, f.device, (torch.float32, torch.uint8), single)
     s = _spatial(radius, sigma, spatial)
     mask, out, cd, st = _outputs(n, h, w, f.device, mask, code, stats, single)
     fn = lib().fotg_flow_filter if g.dtype == torch.float32 else lib().fotg_flow_filter_u8
     check(fn(f.device.index or 0, n, _ptr(f), _ptr(g), w, h, ch, _ptr(mask), radius, s, C.c_float(tau), int(iters), _ptr(out),
              _ptr(cd), _ptr(st), _stream(f.device)))
-    return _result(out, cd, st, single)
+    return unbatch((out, cd, st), single)
 
 
 def upsample_crop_filter_flow(ofc, coarse, guide, mask=None, radius=3, sigma=None, spatial=None, tau=20.0, iters=1, code=None,
@@ -113,24 +82,19 @@ def upsample_crop_filter_flow(ofc, coarse, guide, mask=None, radius=3, sigma=Non
     """The context's coarse flow (n, h_l, w_l, 2) and the guide (n, h_org, w_org[, c]) -> bit for bit
     filter_flow(ofc.upsample_crop(coarse), guide, ...), the statistics included.  fused=True evaluates the upsampling inside the
     filter and never writes the unfiltered full-resolution flow; fused=False runs upsample_crop and the dense filter."""
-    if ofc.nch != 2:
-        raise FotgError("the flow filter needs a two-channel flow (this is a depth-mode context)")
-    n = coarse.shape[0] if isinstance(coarse, torch.Tensor) and coarse.dim() == 4 else 0
-    if n < 1 or n > ofc.max_batch:
-        raise FotgError("coarse must be (n, h_l, w_l, 2) with 1 <= n <= max_batch")
+    n = coarse_flow(ofc, coarse, "the flow filter needs a two-channel flow")
     if not fused:
         return filter_flow(ofc.upsample_crop(coarse), guide, mask=mask, radius=radius, sigma=sigma, spatial=spatial, tau=tau,
                            iters=iters, code=code, stats=stats)
-    wl, hl = ofc.out_size()
-    _dev_f32(coarse, "coarse", ofc.device, (n, hl, wl, 2))
+    coarse_shape(ofc, coarse, "coarse", n)
     h, w = ofc.height_org, ofc.width_org
-    g, ch = _guide(guide, n, h, w, ofc.device, False)
+    g, ch = image_stack(guide, "guide", n, h, w, ofc.device, (torch.float32, torch.uint8))
     s = _spatial(radius, sigma, spatial)
     mask, out, cd, st = _outputs(n, h, w, ofc.device, mask, code, stats, False)
     fn = lib().fotg_upsample_crop_flow_filter if g.dtype == torch.float32 else lib().fotg_upsample_crop_flow_filter_u8
     check(fn(ofc._h, n, _ptr(coarse), _ptr(g), ch, _ptr(mask), radius, s, C.c_float(tau), int(iters), _ptr(out), _ptr(cd), _ptr(st),
              _stream(ofc.device)))
-    return _result(out, cd, st, False)
+    return unbatch((out, cd, st), False)
 
 
 def ofc_calc_filtered(ofc, I0, I1, radius=3, sigma=None, spatial=None, tau=20.0, iters=1, occlusion=True, both=False, code=None,
@@ -141,8 +105,7 @@ def ofc_calc_filtered(ofc, I0, I1, radius=3, sigma=None, spatial=None, tau=20.0,
     returns the backward flow filtered with I1 as guide and mask_bw.  occlusion=False: the fused filter without a mask, on any
     context (both=True then needs a bidir context too).  Returns what upsample_crop_filter_flow returns; with both=True a pair of
     those, (forward, backward)."""
-    if ofc.nch != 2:
-        raise FotgError("the flow filter needs a two-channel flow (this is a depth-mode context)")
+    two_channel(ofc, "the flow filter needs a two-channel flow")
     if (occlusion or both) and not ofc.op.bidir:
         raise FotgError("calc_filtered(occlusion=True) and (both=True) need a context created with opt_params.bidir = True")
     if not isinstance(I0, torch.Tensor) or not isinstance(I1, torch.Tensor) or I0.shape != I1.shape or I0.dim() < 3:
@@ -160,12 +123,5 @@ def ofc_calc_filtered(ofc, I0, I1, radius=3, sigma=None, spatial=None, tau=20.0,
         else:
             fw = ofc.calc_batch_u8(a, b) if u8 else ofc.calc_batch(a, b)
         r = upsample_crop_filter_flow(ofc, fw, a, mask=m, **kw)
-        parts.append((r, upsample_crop_filter_flow(ofc, bw, b, mask=mb, **kw)) if both else (r,))
-
-    def cat(rs):
-        if len(rs) == 1:
-            return rs[0]
-        return torch.cat(rs) if isinstance(rs[0], torch.Tensor) else tuple(torch.cat([r[j] for r in rs]) for j in range(len(rs[0])))
-
-    res = tuple(cat([p[d] for p in parts]) for d in range(2 if both else 1))
-    return res if both else res[0]
+        parts.append((r, upsample_crop_filter_flow(ofc, bw, b, mask=mb, **kw)) if both else r)
+    return cat_chunks(parts)

@@ -6,8 +6,8 @@ Exact integers after the first step (no floating-point atomics: the same bytes e
 include/fotg.h and csrc/histograms.hip.h.  It runs in HIP only; there is no CPU fallback."""
 import torch
 
+from ._args import _ptr, _stream, coarse_flow, coarse_shape, dense_flow, optional, two_channel, unbatch
 from ._lib import FotgError, check, lib
-from .oflow import _dev_f32, _ptr, _stream
 
 # the columns of a record
 HIST = tuple("hof%d" % k for k in range(8)) + ("zero",) + tuple("mbhx%d" % k for k in range(8)) + tuple("mbhy%d" % k for k in range(8)) + (
@@ -35,11 +35,6 @@ def _outputs(n, h, w, cell, rows, cells, ids, device):
             torch.empty((n, rows, len(HIST)), dtype=torch.int64, device=device) if ids is not None else None)
 
 
-def _result(outs, single):
-    outs = [o[0] if single else o for o in outs if o is not None]
-    return outs[0] if len(outs) == 1 else tuple(outs)
-
-
 def motion_histograms(flow, mask=None, motion=None, cell=16, thresh=0.4, ids=None, rows=256, cells=True):
     """flow: device tensor (n, h, w, 2) or (h, w, 2) float32.  mask: None or uint8 (n, h, w) / (h, w), a mask of fb_check (only pixels
     of code 0 take part).  motion: None or float64 (n, 6) / (6,), the parameters fit_motion returns: the camera motion subtracted from
@@ -50,49 +45,34 @@ def motion_histograms(flow, mask=None, motion=None, cell=16, thresh=0.4, ids=Non
     both as a tuple when both.  The 32 columns (HIST): eight HOF bins, the zero-bin pixel count, eight MBHx and eight MBHy bins, then
     the admissible pixels, the pixels in MBH, the inadmissible pixels, the sums of the magnitude, of U and of V in 1/256 pixel, and a
     zero.  A single flow returns them without the batch dimension.  Asynchronous on the current stream."""
-    if not isinstance(flow, torch.Tensor) or flow.dim() not in (3, 4) or flow.shape[-1] != 2:
-        raise FotgError("flow must be a (n, h, w, 2) or (h, w, 2) tensor")
-    single = flow.dim() == 3
     t256 = _args(cell, thresh, rows, cells, ids)
-    f = _dev_f32(flow.unsqueeze(0) if single else flow, "flow")
-    n, h, w = (int(v) for v in f.shape[:3])
-    if n < 1 or h < 1 or w < 1 or h > MAX_DIM or w > MAX_DIM:
-        raise FotgError("flow must have between 1 and %d rows and columns: %s" % (MAX_DIM, tuple(flow.shape)))
-    un = lambda t: t.unsqueeze(0) if single and isinstance(t, torch.Tensor) else t
-    m = None if mask is None else _dev_f32(un(mask), "mask", f.device, (n, h, w), dtype=torch.uint8)
-    p = None if motion is None else _dev_f32(un(motion), "motion", f.device, (n, 6), dtype=torch.float64)
-    i = None if ids is None else _dev_f32(un(ids), "ids", f.device, (n, h, w), dtype=torch.int32)
+    f, single, n, h, w = dense_flow(flow, max_dim=MAX_DIM)
+    m = optional(mask, "mask", f.device, (n, h, w), torch.uint8, single)
+    p = optional(motion, "motion", f.device, (n, 6), torch.float64, single)
+    i = optional(ids, "ids", f.device, (n, h, w), torch.int32, single)
     outs = _outputs(n, h, w, cell, rows, cells, i, f.device)
     check(lib().fotg_motion_histograms(f.device.index or 0, n, _ptr(f), w, h, _ptr(m), _ptr(p), cell, t256, _ptr(outs[0]), _ptr(i), rows,
                                        _ptr(outs[1]), _stream(f.device)))
-    return _result(outs, single)
+    return unbatch(outs, single)
 
 
 def upsample_crop_motion_histograms(ofc, coarse, mask=None, motion=None, cell=16, thresh=0.4, ids=None, rows=256, cells=True, fused=True):
     """The context's coarse flow (n, h_l, w_l, 2), mask and ids of (n, h_org, w_org) -> bit for bit
     motion_histograms(ofc.upsample_crop(coarse), ...).  fused=True evaluates the upsampling inside the kernel and never writes the
     full-resolution flow; fused=False runs upsample_crop and the dense form."""
-    if ofc.nch != 2:
-        raise FotgError("motion histograms need a two-channel flow (this is a depth-mode context)")
-    n = coarse.shape[0] if isinstance(coarse, torch.Tensor) and coarse.dim() == 4 else 0
-    if n < 1 or n > ofc.max_batch:
-        raise FotgError("coarse must be (n, h_l, w_l, 2) with 1 <= n <= max_batch")
+    n = coarse_flow(ofc, coarse, "motion histograms need a two-channel flow")
     if not fused:
         return motion_histograms(ofc.upsample_crop(coarse), mask, motion, cell, thresh, ids, rows, cells)
     t256 = _args(cell, thresh, rows, cells, ids)
-    wl, hl = ofc.out_size()
-    _dev_f32(coarse, "coarse", ofc.device, (n, hl, wl, 2))
+    coarse_shape(ofc, coarse, "coarse", n)
     h, w = ofc.height_org, ofc.width_org
-    if mask is not None:
-        _dev_f32(mask, "mask", ofc.device, (n, h, w), dtype=torch.uint8)
-    if motion is not None:
-        _dev_f32(motion, "motion", ofc.device, (n, 6), dtype=torch.float64)
-    if ids is not None:
-        _dev_f32(ids, "ids", ofc.device, (n, h, w), dtype=torch.int32)
+    optional(mask, "mask", ofc.device, (n, h, w), torch.uint8)
+    optional(motion, "motion", ofc.device, (n, 6), torch.float64)
+    optional(ids, "ids", ofc.device, (n, h, w), torch.int32)
     outs = _outputs(n, h, w, cell, rows, cells, ids, ofc.device)
     check(lib().fotg_upsample_crop_motion_histograms(ofc._h, n, _ptr(coarse), _ptr(mask), _ptr(motion), cell, t256, _ptr(outs[0]), _ptr(ids),
                                                      rows, _ptr(outs[1]), _stream(ofc.device)))
-    return _result(outs, False)
+    return unbatch(outs, False)
 
 
 def motion_descriptors(hist):
@@ -119,8 +99,7 @@ def ofc_motion_histograms(ofc, frames, cell=16, model="affine", occlusion=False,
     max_objects, 32), the object table (T, max_objects, 11), ids (T, h, w)); cells=False leaves the cells out."""
     from .motion import upsample_crop_fit_motion
     from .objects import label_components
-    if ofc.nch != 2:
-        raise FotgError("motion histograms need a two-channel flow (this is a depth-mode context)")
+    two_channel(ofc, "motion histograms need a two-channel flow")
     if objects and model is None:
         raise FotgError("objects=True needs a motion model: the objects are the pixels that do not follow it")
     if occlusion and not ofc.op.bidir:

@@ -9,29 +9,20 @@ import ctypes as C
 
 import torch
 
+from ._args import _dev_f32, _ptr, _stream, batched, coarse_flow, coarse_shape, dense_flow, flow_form, image_stack, optional
 from ._lib import FotgError, check, lib
-from .oflow import _dev_f32, _ptr, _stream
 
 STATS = ("from_forward", "from_backward", "holes", "one_sided", "sum_abs_interpolated", "sum_abs_blend")
 
 
-def _frames(I0, I1, ref, mask_fw, mask_bw, n, h, w, device):
-    """the frames, ref and masks of a batch of n flows of h x w checked: (dtype, channels)"""
-    if not isinstance(I0, torch.Tensor) or I0.dim() not in (3, 4) or I0.dtype not in (torch.float32, torch.uint8):
-        raise FotgError("I0 must be a (n, h, w) or (n, h, w, c) float32 or uint8 tensor")
-    ch = 1 if I0.dim() == 3 else int(I0.shape[3])
-    if ch not in (1, 3) or tuple(I0.shape[:3]) != (n, h, w):
-        raise FotgError("I0 has shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1 | 3)" % (tuple(I0.shape), n, h, w, n, h, w))
-    _dev_f32(I0, "I0", device, dtype=I0.dtype)
-    _dev_f32(I1, "I1", device, tuple(I0.shape), dtype=I0.dtype)
-    if ref is not None:
-        _dev_f32(ref, "ref", device, tuple(I0.shape), dtype=I0.dtype)
+def _frames(I0, I1, ref, mask_fw, mask_bw, n, h, w, device, single):
+    """the frames, ref and masks of a batch of n flows of h x w checked and batched: (I0, I1, ref, mask_fw, mask_bw, channels)"""
+    I0, ch = image_stack(I0, "I0", n, h, w, device, (torch.float32, torch.uint8), single)
+    I1 = _dev_f32(batched(I1, single), "I1", device, I0.shape, I0.dtype)
     if (mask_fw is None) != (mask_bw is None):
         raise FotgError("give both masks or neither")
-    if mask_fw is not None:
-        _dev_f32(mask_fw, "mask_fw", device, (n, h, w), dtype=torch.uint8)
-        _dev_f32(mask_bw, "mask_bw", device, (n, h, w), dtype=torch.uint8)
-    return I0.dtype, ch
+    return (I0, I1, optional(ref, "ref", device, I0.shape, I0.dtype, single), optional(mask_fw, "mask_fw", device, (n, h, w), torch.uint8, single),
+            optional(mask_bw, "mask_bw", device, (n, h, w), torch.uint8, single), ch)
 
 
 def _times(t):
@@ -69,21 +60,12 @@ def interpolate(I0, I1, flow_fw, flow_bw, t, mask_fw=None, mask_bw=None, ref=Non
     pixels whose vector came from the forward flow, from the backward flow, holes, one-sided pixels, sum |ref - dst| and
     sum |ref - ((1 - t) I0 + t I1)| over all pixels and channels (the unrounded values).
     A single (h, w, 3) image is told from a batch (n, h, w) by the flows' dimensions.  Asynchronous on the current stream."""
-    for f, nm in ((flow_fw, "flow_fw"), (flow_bw, "flow_bw")):
-        if not isinstance(f, torch.Tensor) or f.dim() not in (3, 4) or f.shape[-1] != 2:
-            raise FotgError("%s must be a (n, h, w, 2) or (h, w, 2) tensor" % nm)
-    single = flow_fw.dim() == 3
-    if single:
-        un = lambda a: a.unsqueeze(0) if isinstance(a, torch.Tensor) else a
-        I0, I1, flow_fw, flow_bw, mask_fw, mask_bw, ref = (un(a) for a in (I0, I1, flow_fw, flow_bw, mask_fw, mask_bw, ref))
-    n, h, w = (int(v) for v in flow_fw.shape[:3])
-    if n < 1 or h < 1 or w < 1:
-        raise FotgError("flow has an empty dimension: %s" % (tuple(flow_fw.shape),))
-    _dev_f32(flow_fw, "flow_fw")
-    _dev_f32(flow_bw, "flow_bw", flow_fw.device, tuple(flow_fw.shape))
-    dtype, ch = _frames(I0, I1, ref, mask_fw, mask_bw, n, h, w, flow_fw.device)
+    flow_form(flow_bw, "flow_bw")
+    flow_fw, single, n, h, w = dense_flow(flow_fw, "flow_fw")
+    flow_bw = optional(flow_bw, "flow_bw", flow_fw.device, flow_fw.shape, single=single)
+    I0, I1, ref, mask_fw, mask_bw, ch = _frames(I0, I1, ref, mask_fw, mask_bw, n, h, w, flow_fw.device, single)
     ts, seq = _times(t)
-    fn = lib().fotg_interp if dtype == torch.float32 else lib().fotg_interp_u8
+    fn = lib().fotg_interp if I0.dtype == torch.float32 else lib().fotg_interp_u8
     dev = flow_fw.device
 
     def call(tc, dst, code, st):
@@ -98,21 +80,16 @@ def upsample_crop_interpolate(ofc, flow_fw, flow_bw, I0, I1, t, mask_fw=None, ma
     (n, h_org, w_org[, c]) -> byte for byte interpolate(I0, I1, ofc.upsample_crop(flow_fw), ofc.upsample_crop(flow_bw), t, ...),
     the statistics included.  fused=True evaluates the upsampling (and, without masks, the consistency check) inside the call and
     never writes a full-resolution flow; fused=False runs upsample_crop and the dense form."""
-    n = flow_fw.shape[0] if isinstance(flow_fw, torch.Tensor) and flow_fw.dim() == 4 else 0
-    if ofc.nch != 2:
-        raise FotgError("the interpolation needs two-channel flows (this is a depth-mode context)")
-    if n < 1 or n > ofc.max_batch:
-        raise FotgError("flows must be (n, h_l, w_l, 2) with 1 <= n <= max_batch")
+    n = coarse_flow(ofc, flow_fw, "the interpolation needs two-channel flows", "flows")
     if not fused:
         return interpolate(I0, I1, ofc.upsample_crop(flow_fw), ofc.upsample_crop(flow_bw), t, mask_fw=mask_fw, mask_bw=mask_bw,
                            ref=ref, stats=stats, alpha1=alpha1, alpha2=alpha2)
-    wl, hl = ofc.out_size()
-    _dev_f32(flow_fw, "flow_fw", ofc.device, (n, hl, wl, 2))
-    _dev_f32(flow_bw, "flow_bw", ofc.device, (n, hl, wl, 2))
+    coarse_shape(ofc, flow_fw, "flow_fw", n)
+    coarse_shape(ofc, flow_bw, "flow_bw", n)
     h, w = ofc.height_org, ofc.width_org
-    dtype, ch = _frames(I0, I1, ref, mask_fw, mask_bw, n, h, w, ofc.device)
+    I0, I1, ref, mask_fw, mask_bw, ch = _frames(I0, I1, ref, mask_fw, mask_bw, n, h, w, ofc.device, False)
     ts, seq = _times(t)
-    fn = lib().fotg_upsample_crop_interp if dtype == torch.float32 else lib().fotg_upsample_crop_interp_u8
+    fn = lib().fotg_upsample_crop_interp if I0.dtype == torch.float32 else lib().fotg_upsample_crop_interp_u8
 
     def call(tc, dst, code, st):
         check(fn(ofc._h, n, _ptr(flow_fw), _ptr(flow_bw), _ptr(I0), _ptr(I1), ch, tc, _ptr(mask_fw), _ptr(mask_bw), C.c_float(alpha1),

@@ -7,8 +7,8 @@ import ctypes as C
 
 import torch
 
+from ._args import _dev_f32, _ptr, _stream, coarse_flow, coarse_shape, dense_flow, optional, unbatch
 from ._lib import FotgError, check, lib
-from .oflow import _dev_f32, _ptr, _stream
 
 MODELS = ("translation", "similarity", "affine")
 CODES = ("follows", "independent", "masked", "unknown")
@@ -40,11 +40,6 @@ def _fit_outputs(n, h, w, device, code, residual, stats, sums):
             torch.empty((n, 12), dtype=torch.int64, device=device) if sums else None)
 
 
-def _fit_result(outs, single):
-    outs = [o[0] if single else o for o in outs if o is not None]
-    return outs[0] if len(outs) == 1 else tuple(outs)
-
-
 def fit_motion(flow, mask=None, model="affine", iters=3, thresh=1.0, code=False, residual=False, stats=False, sums=False):
     """flow: device tensor (n, h, w, 2) or (h, w, 2) float32; mask: None or uint8 (n, h, w) / (h, w) in the alphabet of fb_check
     (only its code-0 pixels take part).  model: one of MODELS; iters: rounds of re-fitting on the pixels within thresh (pixels) of
@@ -55,23 +50,13 @@ def fit_motion(flow, mask=None, model="affine", iters=3, thresh=1.0, code=False,
     float32 (n, h, w, 2) (flow minus the motion, == flow - motion_flow(params, w, h)), stats int64 (n, 6) (STATS: pixels of code
     0 .. 3, pixels in the last fit, fitted: 1 unless a round had too few pixels or a singular system), sums int64 (n, 12) (SUMS,
     the last round's).  Asynchronous on the current stream of the flow's device."""
-    if not isinstance(flow, torch.Tensor) or flow.dim() not in (3, 4) or flow.shape[-1] != 2:
-        raise FotgError("flow must be a (n, h, w, 2) or (h, w, 2) tensor")
-    single = flow.dim() == 3
-    if single:
-        flow = flow.unsqueeze(0)
-        mask = mask.unsqueeze(0) if isinstance(mask, torch.Tensor) else mask
-    n, h, w = (int(v) for v in flow.shape[:3])
-    if n < 1 or h < 1 or w < 1 or h > MAX_DIM or w > MAX_DIM:
-        raise FotgError("flow must have between 1 and %d rows and columns: %s" % (MAX_DIM, tuple(flow.shape)))
-    _dev_f32(flow, "flow")
-    if mask is not None:
-        _dev_f32(mask, "mask", flow.device, (n, h, w), dtype=torch.uint8)
+    flow, single, n, h, w = dense_flow(flow, max_dim=MAX_DIM)
+    mask = optional(mask, "mask", flow.device, (n, h, w), torch.uint8, single)
     _fit_args(iters, thresh)
     outs = _fit_outputs(n, h, w, flow.device, code, residual, stats, sums)
     check(lib().fotg_fit_motion(flow.device.index or 0, n, _ptr(flow), _ptr(mask), w, h, _model(model), iters, C.c_float(thresh),
                                 *(_ptr(o) for o in outs), _stream(flow.device)))
-    return _fit_result(outs, single)
+    return unbatch(outs, single)
 
 
 def motion_flow(params, w, h):
@@ -97,25 +82,19 @@ def upsample_crop_fit_motion(ofc, flow, mask=None, model="affine", iters=3, thre
     pass and never writes the full-resolution flow; fused=False runs upsample_crop and the dense fit.  The default, None, is the
     form that measured faster on 64 x 1080p: the fused one for iters == 0 (one pass or two: 0.67 against
     0.73 ms), the unfused one otherwise (every further pass pays the upsampling again: 3.37 against 2.85 ms at iters = 3)."""
-    n = flow.shape[0] if isinstance(flow, torch.Tensor) and flow.dim() == 4 else 0
-    if ofc.nch != 2:
-        raise FotgError("the motion fit needs a two-channel flow (this is a depth-mode context)")
-    if n < 1 or n > ofc.max_batch:
-        raise FotgError("flow must be (n, h_l, w_l, 2) with 1 <= n <= max_batch")
+    n = coarse_flow(ofc, flow, "the motion fit needs a two-channel flow", "flow")
     if fused is None:
         fused = iters == 0
     if not fused:
         return fit_motion(ofc.upsample_crop(flow), mask, model, iters, thresh, code, residual, stats, sums)
-    wl, hl = ofc.out_size()
-    _dev_f32(flow, "flow", ofc.device, (n, hl, wl, 2))
+    coarse_shape(ofc, flow, "flow", n)
     h, w = ofc.height_org, ofc.width_org
-    if mask is not None:
-        _dev_f32(mask, "mask", ofc.device, (n, h, w), dtype=torch.uint8)
+    optional(mask, "mask", ofc.device, (n, h, w), torch.uint8)
     _fit_args(iters, thresh)
     outs = _fit_outputs(n, h, w, ofc.device, code, residual, stats, sums)
     check(lib().fotg_upsample_crop_fit_motion(ofc._h, n, _ptr(flow), _ptr(mask), _model(model), iters, C.c_float(thresh),
                                               *(_ptr(o) for o in outs), _stream(ofc.device)))
-    return _fit_result(outs, False)
+    return unbatch(outs, False)
 
 
 def _sequence_flows(ofc, frames):

@@ -7,8 +7,8 @@ import ctypes as C
 
 import torch
 
+from ._args import _dev_f32, _ptr, _stream, optional, two_channel, unbatch
 from ._lib import FotgError, check, lib
-from .oflow import _dev_f32, _ptr, _stream
 
 OBJECT = ("label", "area", "xmin", "ymin", "xmax", "ymax", "sum_x", "sum_y", "n_val", "sum_u", "sum_v")
 OBJECT_STATS = ("foreground", "components", "kept", "written")
@@ -59,13 +59,11 @@ def label_components(code, fg=(1,), connectivity=8, values=None, min_area=1, max
     single = code.dim() == 2
     if single:
         code = code.unsqueeze(0)
-        values = values.unsqueeze(0) if isinstance(values, torch.Tensor) else values
     n, h, w = (int(v) for v in code.shape)
     if n < 1 or h < 1 or w < 1 or h > MAX_DIM or w > MAX_DIM:
         raise FotgError("code must have between 1 and %d rows and columns: %s" % (MAX_DIM, tuple(code.shape)))
     _dev_f32(code, "code", dtype=torch.uint8)
-    if values is not None:
-        _dev_f32(values, "values", code.device, (n, h, w, 2))
+    values = optional(values, "values", code.device, (n, h, w, 2), single=single)
     if connectivity not in (4, 8):
         raise FotgError("connectivity must be 4 or 8")
     if not isinstance(min_area, int) or isinstance(min_area, bool) or min_area < 1:
@@ -79,8 +77,7 @@ def label_components(code, fg=(1,), connectivity=8, values=None, min_area=1, max
             torch.empty((n, len(OBJECT_STATS)), dtype=torch.int64, device=dev) if stats else None)
     check(lib().fotg_label_components(dev.index or 0, n, _ptr(code), w, h, _fg_set(fg), connectivity, _ptr(values), min_area, max_objects,
                                       _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[0]), _ptr(outs[3]), _stream(dev)))
-    res = [o[0] if single else o for o in outs if o is not None]
-    return res[0] if len(res) == 1 else tuple(res)
+    return unbatch(outs, single)
 
 
 def moving_objects(flow, mask=None, model="affine", iters=3, thresh=1.0, min_area=64, max_objects=256, connectivity=8, ids=False,
@@ -111,8 +108,7 @@ def ofc_moving_objects(ofc, frames, model="affine", iters=3, thresh=1.0, min_are
     mask), the motion fit of each with code and residual, then label_components: (params (T, 6), objects (T, max_objects, 11)[,
     ids][, stats])"""
     from .motion import _sequence_flows, upsample_crop_fit_motion
-    if ofc.nch != 2:
-        raise FotgError("the motion fit needs a two-channel flow (this is a depth-mode context)")
+    two_channel(ofc, "the motion fit needs a two-channel flow")
     fw, mask = _sequence_flows(ofc, frames)
     params, code, residual = upsample_crop_fit_motion(ofc, fw, mask, model, iters, thresh, code=True, residual=True)
     out = label_components(code, (1,), connectivity, residual, min_area, max_objects, ids=ids, stats=stats)

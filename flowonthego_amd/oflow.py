@@ -15,6 +15,7 @@ import weakref
 
 import torch
 
+from ._args import _dev_f32, _ptr, _stream
 from ._lib import FotgError, check, lib
 from .params import img_params, opt_params, padded_size
 
@@ -38,27 +39,6 @@ def _close_all():
     # destroy contexts while the HIP runtime is still alive (not from __del__ during interpreter shutdown)
     for o in list(_LIVE):
         o.close()
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(device=None):
-    """the caller's current stream ON THE CONTEXT'S DEVICE (not on whatever device happens to be current)"""
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _dev_f32(t, name, device=None, shape=None, dtype=torch.float32):
-    """The C-ABI takes raw pointers and trusts the sizes: everything a kernel will read or write is checked here --
-    dtype, contiguity, device and, where the caller knows it, the exact shape."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        raise FotgError("%s must be a contiguous %s CUDA(HIP) tensor" % (name, str(dtype).replace("torch.", "")))
-    if device is not None and t.device != device:
-        raise FotgError("%s lives on %s, the context on %s" % (name, t.device, device))
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise FotgError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-    return t
 
 
 class OFClass:

@@ -10,8 +10,8 @@ import ctypes as C
 
 import torch
 
+from ._args import _dev_f32, _ptr, _stream, cat_chunks, coarse_shape, image_stack, optional, two_channel
 from ._lib import FotgError, callable_module, check, lib
-from .oflow import _dev_f32, _ptr, _stream
 
 STATS = ("sum_used", "unfiltered", "sum_abs_filtered", "sum_abs_center")
 MAX_NEIGHBORS = 8
@@ -45,12 +45,7 @@ def _indices(center, neighbors):
 
 def _frames(frames, device=None):
     """the stack checked: (T, h, w, channels, dtype)"""
-    if not isinstance(frames, torch.Tensor) or frames.dim() not in (3, 4) or frames.dtype not in (torch.float32, torch.uint8):
-        raise FotgError("frames must be a (T, h, w) or (T, h, w, c) float32 or uint8 tensor")
-    ch = 1 if frames.dim() == 3 else int(frames.shape[3])
-    if ch not in (1, 3) or min(frames.shape) < 1:
-        raise FotgError("frames has shape %s, expected (T, h, w) or (T, h, w, 1 | 3), nothing empty" % (tuple(frames.shape),))
-    _dev_f32(frames, "frames", device, dtype=frames.dtype)
+    frames, ch = image_stack(frames, "frames", None, None, None, device, (torch.float32, torch.uint8))
     return int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2]), ch, frames.dtype
 
 
@@ -65,11 +60,9 @@ def _gains(gains, K):
 
 def _rest(frames, n, K, h, w, masks, ref, stats):
     """masks and ref checked, the outputs allocated: (dst, used, st)"""
-    if masks is not None:
-        _dev_f32(masks, "masks", frames.device, (n, K, h, w), dtype=torch.uint8)
+    optional(masks, "masks", frames.device, (n, K, h, w), torch.uint8)
     shape = (n,) + tuple(frames.shape[1:])
-    if ref is not None:
-        _dev_f32(ref, "ref", frames.device, shape, dtype=frames.dtype)
+    optional(ref, "ref", frames.device, shape, frames.dtype)
     dst = torch.empty(shape, dtype=frames.dtype, device=frames.device)
     used = torch.empty((n, h, w), dtype=torch.uint8, device=frames.device) if stats else None
     st = torch.empty((n, 4), dtype=torch.float64, device=frames.device) if stats else None
@@ -103,14 +96,12 @@ def upsample_crop_temporal_filter(ofc, coarse_flows, frames, center, neighbors, 
     image-major -- and frames (T, h_org, w_org[, c]) -> bit for bit temporal_filter(frames, center, neighbors,
     ofc.upsample_crop(coarse_flows).view(n, K, h, w, 2), ...), the statistics included.  fused=True evaluates the upsampling inside
     the filter and never writes a full-resolution flow; fused=False runs upsample_crop and the dense filter."""
-    if ofc.nch != 2:
-        raise FotgError("the temporal filter needs a two-channel flow (this is a depth-mode context)")
+    two_channel(ofc, "the temporal filter needs a two-channel flow")
     T, h, w, ch, dtype = _frames(frames, ofc.device)
     n, K, cen, nbr = _indices(center, neighbors)
     if n * K > ofc.max_batch:
         raise FotgError("%d images x %d neighbours, context created for max_batch = %d" % (n, K, ofc.max_batch))
-    wl, hl = ofc.out_size()
-    _dev_f32(coarse_flows, "coarse_flows", ofc.device, (n * K, hl, wl, 2))
+    coarse_shape(ofc, coarse_flows, "coarse_flows", n * K)
     if (h, w) != (ofc.height_org, ofc.width_org):
         raise FotgError("frames are %d x %d, the context is %d x %d" % (w, h, ofc.width_org, ofc.height_org))
     if not fused:
@@ -137,8 +128,7 @@ def ofc_temporal_filter(ofc, frames, radius=1, tau=30.0, gains=None, occlusion=F
     centres per batch, and the fused filter applied.  occlusion=True (a bidir context) also computes the flows neighbour -> centre
     and lets only the pixels the forward-backward check finds consistent take part.  ref: None or the clean stack, for the
     statistics.  Returns dst (T, ...) or (dst, used (T, h, w), stats (T, 4))."""
-    if ofc.nch != 2:
-        raise FotgError("the temporal filter needs a two-channel flow (this is a depth-mode context)")
+    two_channel(ofc, "the temporal filter needs a two-channel flow")
     T, h, w, ch, dtype = _frames(frames, ofc.device)
     if not isinstance(radius, int) or not 1 <= 2 * radius <= MAX_NEIGHBORS:
         raise FotgError("radius must be 1 .. %d" % (MAX_NEIGHBORS // 2))
@@ -148,8 +138,7 @@ def ofc_temporal_filter(ofc, frames, radius=1, tau=30.0, gains=None, occlusion=F
     per = ofc.max_batch // K
     if per < 1:
         raise FotgError("a radius of %d needs a context with max_batch >= %d" % (radius, K))
-    if ref is not None:
-        _dev_f32(ref, "ref", ofc.device, tuple(frames.shape), dtype=dtype)
+    optional(ref, "ref", ofc.device, frames.shape, dtype)
     u8 = dtype == torch.uint8
     center, neighbors = neighbor_table(T, radius)
     outs = []
@@ -168,9 +157,7 @@ def ofc_temporal_filter(ofc, frames, radius=1, tau=30.0, gains=None, occlusion=F
             fw = ofc.calc_batch_u8(I0, I1) if u8 else ofc.calc_batch(I0, I1)
         outs.append(upsample_crop_temporal_filter(ofc, fw, frames, cen, nbr, masks=masks, tau=tau, gains=gains,
                                                   ref=None if ref is None else ref[s:s + n], stats=stats))
-    if not stats:
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
-    return tuple(torch.cat([o[j] for o in outs]) for j in range(3))
+    return cat_chunks(outs)
 
 
 callable_module(__name__, __name__, "temporal_filter")

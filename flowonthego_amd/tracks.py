@@ -7,9 +7,9 @@ integers throughout (no floating-point atomics: the same bytes every run); the d
 csrc/objtracks.hip.h.  It runs in HIP only; there is no CPU fallback."""
 import torch
 
+from ._args import _dev_f32, _ptr, _stream, batched, coarse_flow, coarse_shape, dense_flow, optional, two_channel, unbatch
 from ._lib import FotgError, check, lib
 from .objects import OBJECT
-from .oflow import _dev_f32, _ptr, _stream
 
 TRACK = ("first_frame", "last_frame", "first_row", "last_row", "sum_area", "max_area", "sum_votes", "end")
 TRACK_STATS = ("started", "recorded", "links", "alive")
@@ -46,43 +46,30 @@ def object_overlap(ids_a, ids_b, flow, mask=None, ka=256, kb=256):
     object j of b; sent int64 (n, ka, 4) (SENT): per object of a the pixels that voted, landed on background, left the frame, or had
     no admissible vector (masked, not finite, beyond +-4096).  A single pair returns both without the batch dimension.  Asynchronous
     on the current stream."""
-    if not isinstance(flow, torch.Tensor) or flow.dim() not in (3, 4) or flow.shape[-1] != 2:
-        raise FotgError("flow must be a (n, h, w, 2) or (h, w, 2) tensor")
-    single = flow.dim() == 3
     ka, kb = _rows(ka, "ka"), _rows(kb, "kb")
-    f = _dev_f32(flow.unsqueeze(0) if single else flow, "flow")
-    n, h, w = (int(v) for v in f.shape[:3])
-    if n < 1 or h < 1 or w < 1:
-        raise FotgError("flow has an empty dimension: %s" % (tuple(flow.shape),))
-    un = lambda t: t.unsqueeze(0) if single and isinstance(t, torch.Tensor) else t
-    a = _dev_f32(un(ids_a), "ids_a", f.device, (n, h, w), dtype=torch.int32)
-    b = _dev_f32(un(ids_b), "ids_b", f.device, (n, h, w), dtype=torch.int32)
-    m = None if mask is None else _dev_f32(un(mask), "mask", f.device, (n, h, w), dtype=torch.uint8)
+    f, single, n, h, w = dense_flow(flow)
+    a = _dev_f32(batched(ids_a, single), "ids_a", f.device, (n, h, w), torch.int32)
+    b = _dev_f32(batched(ids_b, single), "ids_b", f.device, (n, h, w), torch.int32)
+    m = optional(mask, "mask", f.device, (n, h, w), torch.uint8, single)
     votes, sent = _overlap_outputs(n, ka, kb, f.device)
     check(lib().fotg_object_overlap(f.device.index or 0, n, _ptr(a), _ptr(b), w, h, _ptr(f), _ptr(m), ka, kb, _ptr(votes), _ptr(sent),
                                     _stream(f.device)))
-    return (votes[0], sent[0]) if single else (votes, sent)
+    return unbatch((votes, sent), single, always_tuple=True)
 
 
 def upsample_crop_object_overlap(ofc, coarse, ids_a, ids_b, mask=None, ka=256, kb=256, fused=True):
     """The context's coarse flow (n, h_l, w_l, 2) and the ids of the frames (n, h_org, w_org) -> bit for bit
     object_overlap(ids_a, ids_b, ofc.upsample_crop(coarse), ...).  fused=True evaluates the upsampling inside the kernel and never
     writes the full-resolution flow; fused=False runs upsample_crop and the dense form."""
-    if ofc.nch != 2:
-        raise FotgError("object tracks need a two-channel flow (this is a depth-mode context)")
-    n = coarse.shape[0] if isinstance(coarse, torch.Tensor) and coarse.dim() == 4 else 0
-    if n < 1 or n > ofc.max_batch:
-        raise FotgError("coarse must be (n, h_l, w_l, 2) with 1 <= n <= max_batch")
+    n = coarse_flow(ofc, coarse, "object tracks need a two-channel flow")
     if not fused:
         return object_overlap(ids_a, ids_b, ofc.upsample_crop(coarse), mask=mask, ka=ka, kb=kb)
     ka, kb = _rows(ka, "ka"), _rows(kb, "kb")
-    wl, hl = ofc.out_size()
-    _dev_f32(coarse, "coarse", ofc.device, (n, hl, wl, 2))
+    coarse_shape(ofc, coarse, "coarse", n)
     h, w = ofc.height_org, ofc.width_org
     _dev_f32(ids_a, "ids_a", ofc.device, (n, h, w), dtype=torch.int32)
     _dev_f32(ids_b, "ids_b", ofc.device, (n, h, w), dtype=torch.int32)
-    if mask is not None:
-        _dev_f32(mask, "mask", ofc.device, (n, h, w), dtype=torch.uint8)
+    optional(mask, "mask", ofc.device, (n, h, w), torch.uint8)
     votes, sent = _overlap_outputs(n, ka, kb, ofc.device)
     check(lib().fotg_upsample_crop_object_overlap(ofc._h, n, _ptr(coarse), _ptr(ids_a), _ptr(ids_b), _ptr(mask), ka, kb, _ptr(votes),
                                                   _ptr(sent), _stream(ofc.device)))
@@ -100,19 +87,18 @@ def object_links(votes, objects_a, objects_b, min_votes=16, min_frac=0.25):
         raise FotgError("votes must be a (n, ka, kb) or (ka, kb) tensor")
     min_votes, frac256 = _thresholds(min_votes, min_frac)
     single = votes.dim() == 2
-    un = lambda t: t.unsqueeze(0) if single and isinstance(t, torch.Tensor) else t
-    v = _dev_f32(un(votes), "votes", dtype=torch.int32)
+    v = _dev_f32(batched(votes, single), "votes", dtype=torch.int32)
     n, ka, kb = (int(x) for x in v.shape)
     if n < 1:
         raise FotgError("votes has an empty dimension: %s" % (tuple(votes.shape),))
     _rows(ka, "ka"), _rows(kb, "kb")
-    oa = _dev_f32(un(objects_a), "objects_a", v.device, (n, ka, len(OBJECT)), dtype=torch.int64)
-    ob = _dev_f32(un(objects_b), "objects_b", v.device, (n, kb, len(OBJECT)), dtype=torch.int64)
+    oa = _dev_f32(batched(objects_a, single), "objects_a", v.device, (n, ka, len(OBJECT)), torch.int64)
+    ob = _dev_f32(batched(objects_b, single), "objects_b", v.device, (n, kb, len(OBJECT)), torch.int64)
     ab = torch.empty((n, ka, 3), dtype=torch.int32, device=v.device)
     ba = torch.empty((n, kb, 3), dtype=torch.int32, device=v.device)
     check(lib().fotg_object_links(v.device.index or 0, n, _ptr(v), _ptr(oa), _ptr(ob), ka, kb, min_votes, frac256, _ptr(ab), _ptr(ba),
                                   _stream(v.device)))
-    return (ab[0], ba[0]) if single else (ab, ba)
+    return unbatch((ab, ba), single, always_tuple=True)
 
 
 def link_tracks(objects, link_ab, link_ba, max_tracks=1024, stats=False):
@@ -176,8 +162,7 @@ def ofc_track_objects(ofc, frames, model="affine", iters=3, thresh=1.0, min_area
     give T object maps and T-1 links; at least three frames."""
     from .motion import _sequence_flows, upsample_crop_fit_motion
     from .objects import label_components
-    if ofc.nch != 2:
-        raise FotgError("object tracks need a two-channel flow (this is a depth-mode context)")
+    two_channel(ofc, "object tracks need a two-channel flow")
     if not isinstance(frames, torch.Tensor) or frames.shape[0] < 3:
         raise FotgError("track_objects needs at least three frames")
     _rows(max_objects, "max_objects")

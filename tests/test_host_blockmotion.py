@@ -10,25 +10,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_checks import cli_refuses, entry_points, resource_table
 
 NEW_SYMBOLS = ("fotg_block_motion", "fotg_upsample_crop_block_motion")
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    import flowonthego_amd as F
-    from flowonthego_amd._lib import SYMBOLS
-    L = F.lib()
-    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
-    bound = {s[0]: s for s in SYMBOLS}
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in bound and hasattr(L, name)
-        # one ctypes argument per parameter of the declaration
-        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
-        assert len(decl.split(",")) == len(bound[name][2]), name
-    shim = open(os.path.join(ROOT, "include", "fotg", "blockmotion.h")).read()
-    for name in NEW_SYMBOLS:
-        assert name + "(" in shim
+    F, _ = entry_points(NEW_SYMBOLS, "blockmotion.h")
     assert callable(F.block_motion) and callable(F.upsample_crop_block_motion)
     from flowonthego_amd.blockmotion import block_motion, upsample_crop_block_motion
     assert F.upsample_crop_block_motion is upsample_crop_block_motion and callable(block_motion)
@@ -44,22 +32,14 @@ def test_block_motion_example_builds(tmp_path):
 
 
 def test_cli_argument_errors(tmp_path):
-    env = dict(os.environ, PYTHONPATH=ROOT)
     base = ["c.npy", "r.npy", "f.flo", "o.npz"]
-    for args in ([], ["c.npy"], base[:2], base[:3], base + ["extra"], base + ["--block", "x"], base + ["--block", "12"],
-                 base + ["--block", "64"], base + ["--block"], base + ["--refine", "4"], base + ["--refine", "-1"],
-                 base + ["--refine", "1.5"], base + ["--refine"], base + ["--bw"], base + ["--pred"], base + ["--nosuch"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.block_motion"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
-        assert r.returncode != 0 and "usage" in r.stderr, args
+    cli_refuses("block_motion", ([], ["c.npy"], base[:2], base[:3], base + ["extra"], base + ["--block", "x"], base + ["--block", "12"],
+                                 base + ["--block", "64"], base + ["--block"], base + ["--refine", "4"], base + ["--refine", "-1"],
+                                 base + ["--refine", "1.5"], base + ["--refine"], base + ["--bw"], base + ["--pred"], base + ["--nosuch"]))
 
 
 def test_resource_table_lists_the_blockmv_kernels_without_scratch():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
-    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
-    assert len(names) == len(scratch)
-    table = dict(zip(names, scratch))
+    names, table = resource_table()
     # Src x channels x block, Itanium-mangled: blockmv_kernel<DenseSrc | UpsampleSrc, 1 | 3, 8 | 16 | 32>
     for src in ("NS_8DenseSrcE", "NS_11UpsampleSrcE"):
         for noc in (1, 3):

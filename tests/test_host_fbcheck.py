@@ -11,6 +11,7 @@ import pytest
 
 import fbcheck_ref as R
 from conftest import ROOT
+from host_checks import cli_refuses
 
 
 def test_fb_check_example_builds(tmp_path):
@@ -21,10 +22,7 @@ def test_fb_check_example_builds(tmp_path):
 
 
 def test_cli_argument_errors(tmp_path):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    for args in ([], ["a.flo"], ["a.flo", "b.flo"], ["a.flo", "b.flo", "c.png", "--alpha1", "x"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.fb_check"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
-        assert r.returncode != 0 and "usage" in r.stderr, args
+    cli_refuses("fb_check", ([], ["a.flo"], ["a.flo", "b.flo"], ["a.flo", "b.flo", "c.png", "--alpha1", "x"]))
 
 
 def read_png_rgb(path):

@@ -10,26 +10,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_checks import cli_refuses, entry_points, resource_table
 
 NEW_SYMBOLS = ("fotg_flow_filter", "fotg_flow_filter_u8", "fotg_upsample_crop_flow_filter", "fotg_upsample_crop_flow_filter_u8")
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    import flowonthego_amd as F
-    from flowonthego_amd._lib import SYMBOLS
-    L = F.lib()
-    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
-    bound = {s[0]: s for s in SYMBOLS}
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in bound and hasattr(L, name)
-    # one ctypes argument per parameter of the declaration
-    for name in NEW_SYMBOLS:
-        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
-        assert len(decl.split(",")) == len(bound[name][2]), name
-    shim = open(os.path.join(ROOT, "include", "fotg", "flowfilter.h")).read()
-    for name in NEW_SYMBOLS:
-        assert name + "(" in shim
+    F, _ = entry_points(NEW_SYMBOLS, "flowfilter.h")
     assert callable(F.filter_flow) and callable(F.upsample_crop_filter_flow) and callable(F.spatial_table)
     from flowonthego_amd.oflow import OFClass
     assert callable(OFClass.calc_filtered) and callable(OFClass.upsample_crop_filter_flow)
@@ -53,23 +40,15 @@ def test_filter_flow_example_builds(tmp_path):
 
 
 def test_cli_argument_errors(tmp_path):
-    env = dict(os.environ, PYTHONPATH=ROOT)
     base = ["a.flo", "g.npy", "o.flo"]
-    for args in ([], ["a.flo"], ["a.flo", "g.npy"], base + ["extra"], base + ["--radius", "x"], base + ["--radius", "0"],
-                 base + ["--radius", "8"], base + ["--iters", "0"], base + ["--iters", "5"], base + ["--tau", "0"],
-                 base + ["--tau", "nan"], base + ["--tau"], base + ["--sigma", "0"], base + ["--sigma", "-1"], base + ["--bw"],
-                 base + ["--code"], base + ["--nosuch"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.filter_flow"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
-        assert r.returncode != 0 and "usage" in r.stderr, args
+    cli_refuses("filter_flow", ([], ["a.flo"], ["a.flo", "g.npy"], base + ["extra"], base + ["--radius", "x"], base + ["--radius", "0"],
+                                base + ["--radius", "8"], base + ["--iters", "0"], base + ["--iters", "5"], base + ["--tau", "0"],
+                                base + ["--tau", "nan"], base + ["--tau"], base + ["--sigma", "0"], base + ["--sigma", "-1"], base + ["--bw"],
+                                base + ["--code"], base + ["--nosuch"]))
 
 
 def test_resource_table_lists_the_flowfilter_kernels_without_scratch():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
-    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
-    assert len(names) == len(scratch)
-    table = dict(zip(names, scratch))
+    names, table = resource_table()
     # Src x guide type x channels, Itanium-mangled: flowfilter_kernel<DenseSrc | UpsampleSrc, float | unsigned char, 1 | 3>
     for src in ("NS_8DenseSrcE", "NS_11UpsampleSrcE"):
         for t in ("f", "h"):

@@ -4,33 +4,20 @@ without a private-memory segment, and the arguments the entry points refuse are 
 the CLI writes what the calls return."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 
 import pytest
 
 from conftest import ROOT
+from host_checks import entry_points, resource_table
 
 NEW_SYMBOLS = ("fotg_motion_histograms", "fotg_upsample_crop_motion_histograms")
 FOTG_ERR_ARG = 1
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    import flowonthego_amd as F
-    from flowonthego_amd._lib import SYMBOLS
-    L = F.lib()
-    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
-    bound = {s[0]: s for s in SYMBOLS}
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in bound and hasattr(L, name)
-        # one ctypes argument per parameter of the declaration
-        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
-        assert len(decl.split(",")) == len(bound[name][2]), name
-    shim = open(os.path.join(ROOT, "include", "fotg", "histograms.h")).read()
-    for name in NEW_SYMBOLS:
-        assert name + "(" in shim
+    F, hdr = entry_points(NEW_SYMBOLS, "histograms.h")
     from flowonthego_amd import histograms
     for name in ("upsample_crop_motion_histograms", "motion_descriptors"):
         assert getattr(F, name) is getattr(histograms, name) and callable(getattr(F, name))
@@ -60,12 +47,7 @@ def test_motion_histograms_example_builds(tmp_path):
 
 
 def test_resource_table_lists_the_histogram_kernels_without_scratch():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
-    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
-    assert len(names) == len(scratch)
-    table = dict(zip(names, scratch))
+    names, table = resource_table()
     mine = sorted(n for n in names if "mh_kernel" in n)
     # Itanium-mangled: mh_kernel<DenseSrc | UpsampleSrc> -- and nothing else
     want = ["mh_kernelINS_8DenseSrcEEE", "mh_kernelINS_11UpsampleSrcEEE"]

@@ -4,7 +4,6 @@ the compiler's resource table lists every interpolation kernel without a private
 restatement's frame."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 
@@ -13,25 +12,14 @@ import pytest
 
 import interp_ref as I
 from conftest import ROOT
+from host_checks import cli_refuses, entry_points, resource_table
 
 NEW_SYMBOLS = ("fotg_interp", "fotg_interp_u8", "fotg_upsample_crop_interp", "fotg_upsample_crop_interp_u8")
 FOTG_ERR_ARG = 1
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    import flowonthego_amd as F
-    from flowonthego_amd._lib import SYMBOLS
-    L = F.lib()
-    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
-    bound = {s[0]: s for s in SYMBOLS}
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in bound and hasattr(L, name)
-        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
-        assert len(decl.split(",")) == len(bound[name][2]), name
-    shim = open(os.path.join(ROOT, "include", "fotg", "interp.h")).read()
-    for name in NEW_SYMBOLS:
-        assert name + "(" in shim
+    F, _ = entry_points(NEW_SYMBOLS, "interp.h")
     assert callable(F.interpolate) and callable(F.upsample_crop_interpolate)
     from flowonthego_amd.oflow import OFClass
     assert all(hasattr(OFClass, m) for m in ("interpolate", "upsample_crop_interpolate", "bidirectional_flows"))
@@ -64,20 +52,12 @@ def test_interp_frame_example_builds(tmp_path):
 
 
 def test_cli_argument_errors():
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    for args in ([], ["a.npy"], ["a.npy", "b.npy", "0.5"], ["a.npy", "b.npy", "x", "d.png"], ["a.npy", "b.npy", "1.0", "d.png"],
-                 ["a.npy", "b.npy", "0", "d.png"], ["a.npy", "b.npy", "0.5", "d.png", "--ref"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.interp_frame"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
-        assert r.returncode != 0 and "usage" in r.stderr, args
+    cli_refuses("interp_frame", ([], ["a.npy"], ["a.npy", "b.npy", "0.5"], ["a.npy", "b.npy", "x", "d.png"], ["a.npy", "b.npy", "1.0", "d.png"],
+                                 ["a.npy", "b.npy", "0", "d.png"], ["a.npy", "b.npy", "0.5", "d.png", "--ref"]))
 
 
 def test_resource_table_lists_the_interpolation_kernels_without_scratch():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
-    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
-    assert len(names) == len(scratch)
-    table = dict(zip(names, scratch))
+    names, table = resource_table()
     for kernel in ("23interp_candidate_kernel", "21interp_resolve_kernel"):
         for src in ("NS_8DenseSrcE", "NS_11UpsampleSrcE"):
             for t in ("f", "h"):

@@ -2,32 +2,18 @@
 against the C++ shim, the two command-line tools refuse bad arguments, and the compiler's resource table lists every instantiation
 of the motion kernels without a private-memory segment."""
 import os
-import re
 import subprocess
-import sys
 
 import numpy as np
 
 from conftest import ROOT
+from host_checks import cli_refuses, entry_points, resource_table
 
 NEW_SYMBOLS = ("fotg_fit_motion", "fotg_upsample_crop_fit_motion", "fotg_motion_flow", "fotg_motion_ending")
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    import flowonthego_amd as F
-    from flowonthego_amd._lib import SYMBOLS
-    L = F.lib()
-    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
-    bound = {s[0]: s for s in SYMBOLS}
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in bound and hasattr(L, name)
-        # one ctypes argument per parameter of the declaration
-        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
-        assert len(decl.split(",")) == len(bound[name][2]), name
-    shim = open(os.path.join(ROOT, "include", "fotg", "motion.h")).read()
-    for name in NEW_SYMBOLS[:3]:
-        assert name + "(" in shim
+    F, hdr = entry_points(NEW_SYMBOLS, "motion.h", in_shim=NEW_SYMBOLS[:3])
     for name in ("fit_motion", "motion_flow", "upsample_crop_fit_motion", "stabilize", "smoothing_motions"):
         assert callable(getattr(F, name)), name
     assert F.MODELS == ("translation", "similarity", "affine") and len(F.CODES) == 4
@@ -64,15 +50,12 @@ def test_fit_motion_example_builds(tmp_path):
 
 
 def test_cli_argument_errors(tmp_path):
-    env = dict(os.environ, PYTHONPATH=ROOT)
     bad = {"fit_motion": ([], ["a.flo", "b.flo"], ["a.flo", "--model", "projective"], ["a.flo", "--iters", "-1"], ["a.flo", "--thresh", "-2"],
                           ["a.flo", "--mask"]),
            "stabilize": ([], ["frames.npy"], ["frames.npy", "out.npy", "--model", "homography"], ["frames.npy", "out.npy", "--radius", "-1"],
                          ["frames.npy", "out.npy", "extra.npy"])}
     for tool, cases in bad.items():
-        for args in cases:
-            r = subprocess.run([sys.executable, "-m", "flowonthego_amd." + tool] + args, capture_output=True, text=True, cwd=ROOT, env=env)
-            assert r.returncode != 0 and "usage" in r.stderr, (tool, args)
+        cli_refuses(tool, cases)
 
 
 def test_gray_png_reader_reads_every_filter(tmp_path):
@@ -102,12 +85,7 @@ def test_gray_png_reader_reads_every_filter(tmp_path):
 
 
 def test_resource_table_lists_the_motion_kernels_without_scratch():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
-    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
-    assert len(names) == len(scratch)
-    table = dict(zip(names, scratch))
+    names, table = resource_table()
     # Itanium-mangled: motion_pass_kernel<DenseSrc | UpsampleSrc, round 0 | later round | final>, motion_fold_kernel<12 | 4>
     want = ["motion_pass_kernelI%sLi%dE" % (src, p) for src in ("NS_8DenseSrcE", "NS_11UpsampleSrcE") for p in (0, 1, 2)]
     want += ["motion_fold_kernelILi12E", "motion_fold_kernelILi4E", "motion_solve_kernelE", "motion_flow_kernelE"]

@@ -10,27 +10,14 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_checks import cli_refuses, entry_points, resource_table
 
 NEW_SYMBOLS = ("fotg_temporal_filter", "fotg_temporal_filter_u8", "fotg_upsample_crop_temporal_filter",
                "fotg_upsample_crop_temporal_filter_u8")
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    import flowonthego_amd as F
-    from flowonthego_amd._lib import SYMBOLS
-    L = F.lib()
-    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
-    bound = {s[0]: s for s in SYMBOLS}
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in bound and hasattr(L, name)
-    # one ctypes argument per parameter of the declaration
-    for name in NEW_SYMBOLS:
-        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
-        assert len(decl.split(",")) == len(bound[name][2]), name
-    shim = open(os.path.join(ROOT, "include", "fotg", "temporal.h")).read()
-    for name in NEW_SYMBOLS:
-        assert name + "(" in shim
+    F, _ = entry_points(NEW_SYMBOLS, "temporal.h")
     assert callable(F.temporal_filter) and callable(F.upsample_crop_temporal_filter)
     from flowonthego_amd.oflow import OFClass
     import flowonthego_amd.temporal as TM
@@ -53,21 +40,13 @@ def test_temporal_filter_example_builds(tmp_path):
 
 
 def test_cli_argument_errors(tmp_path):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    for args in ([], ["a.npy"], ["a.npy", "b.npy", "c.npy"], ["a.npy", "b.npy", "--radius", "x"], ["a.npy", "b.npy", "--radius", "0"],
-                 ["a.npy", "b.npy", "--radius", "5"], ["a.npy", "b.npy", "--tau", "0"], ["a.npy", "b.npy", "--tau"],
-                 ["a.npy", "b.npy", "--ref"], ["a.npy", "b.npy", "--nosuch"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.denoise"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
-        assert r.returncode != 0 and "usage" in r.stderr, args
+    cli_refuses("denoise", ([], ["a.npy"], ["a.npy", "b.npy", "c.npy"], ["a.npy", "b.npy", "--radius", "x"], ["a.npy", "b.npy", "--radius", "0"],
+                            ["a.npy", "b.npy", "--radius", "5"], ["a.npy", "b.npy", "--tau", "0"], ["a.npy", "b.npy", "--tau"],
+                            ["a.npy", "b.npy", "--ref"], ["a.npy", "b.npy", "--nosuch"]))
 
 
 def test_resource_table_lists_the_temporal_kernels_without_scratch():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
-    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
-    assert len(names) == len(scratch)
-    table = dict(zip(names, scratch))
+    names, table = resource_table()
     # Src x element type x channels, Itanium-mangled: temporal_kernel<DenseSrc | UpsampleSrc, float | unsigned char, 1 | 3>
     for src in ("NS_8DenseSrcE", "NS_11UpsampleSrcE"):
         for t in ("f", "h"):

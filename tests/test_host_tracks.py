@@ -11,26 +11,14 @@ import sys
 import pytest
 
 from conftest import ROOT
+from host_checks import cli_refuses, entry_points, resource_table
 
 NEW_SYMBOLS = ("fotg_object_overlap", "fotg_upsample_crop_object_overlap", "fotg_object_links", "fotg_object_tracks")
 FOTG_ERR_ARG = 1
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    import flowonthego_amd as F
-    from flowonthego_amd._lib import SYMBOLS
-    L = F.lib()
-    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
-    bound = {s[0]: s for s in SYMBOLS}
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in bound and hasattr(L, name)
-        # one ctypes argument per parameter of the declaration
-        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
-        assert len(decl.split(",")) == len(bound[name][2]), name
-    shim = open(os.path.join(ROOT, "include", "fotg", "tracks.h")).read()
-    for name in NEW_SYMBOLS:
-        assert name + "(" in shim
+    F, _ = entry_points(NEW_SYMBOLS, "tracks.h")
     from flowonthego_amd import tracks
     for name in ("object_overlap", "upsample_crop_object_overlap", "object_links", "link_tracks"):
         assert getattr(F, name) is getattr(tracks, name) and callable(getattr(F, name))
@@ -48,21 +36,13 @@ def test_track_objects_example_builds(tmp_path):
 
 
 def test_cli_argument_errors():
-    env = dict(os.environ, PYTHONPATH=ROOT)
     base = ["f.npy", "o.npz"]
-    for args in ([], base[:1], base + ["extra"], base + ["--model", "rigid"], base + ["--min-area", "0"], base + ["--min-votes", "0"],
-                 base + ["--min-frac", "1.5"], base + ["--max-objects", "1025"], base + ["--ids"], base + ["--nosuch"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.track_objects"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
-        assert r.returncode != 0 and "usage" in r.stderr, args
+    cli_refuses("track_objects", ([], base[:1], base + ["extra"], base + ["--model", "rigid"], base + ["--min-area", "0"], base + ["--min-votes", "0"],
+                                  base + ["--min-frac", "1.5"], base + ["--max-objects", "1025"], base + ["--ids"], base + ["--nosuch"]))
 
 
 def test_resource_table_lists_the_object_track_kernels_without_scratch():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
-    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
-    assert len(names) == len(scratch)
-    table = dict(zip(names, scratch))
+    names, table = resource_table()
     mine = sorted(n for n in names if re.search(r"obj(vote|link|track)", n))
     # Itanium-mangled: objvote_kernel<DenseSrc | UpsampleSrc>, objlink_kernel, objtrack_kernel -- and nothing else
     want = ["objvote_kernelINS_8DenseSrcEEE", "objvote_kernelINS_11UpsampleSrcEEE", "14objlink_kernelE", "15objtrack_kernelE"]

@@ -2,7 +2,6 @@
 the C++ shim, the CLI refuses bad arguments, and the compiler's resource table lists every warp_kernel instantiation without a
 private-memory segment.  With a GPU: the CLI writes the restatement's frame and prints its numbers."""
 import os
-import re
 import subprocess
 import sys
 
@@ -11,26 +10,13 @@ import pytest
 
 import warp_ref as W
 from conftest import ROOT
+from host_checks import cli_refuses, entry_points, resource_table
 
 NEW_SYMBOLS = ("fotg_warp", "fotg_warp_u8", "fotg_upsample_crop_warp", "fotg_upsample_crop_warp_u8")
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    import flowonthego_amd as F
-    from flowonthego_amd._lib import SYMBOLS
-    L = F.lib()
-    hdr = open(os.path.join(ROOT, "include", "fotg.h")).read()
-    bound = {s[0]: s for s in SYMBOLS}
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in bound and hasattr(L, name)
-    # one ctypes argument per parameter of the declaration
-    for name in NEW_SYMBOLS:
-        decl = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
-        assert len(decl.split(",")) == len(bound[name][2]), name
-    shim = open(os.path.join(ROOT, "include", "fotg", "warp.h")).read()
-    for name in NEW_SYMBOLS:
-        assert name + "(" in shim
+    F, _ = entry_points(NEW_SYMBOLS, "warp.h")
     assert callable(F.warp) and callable(F.upsample_crop_warp)
 
 
@@ -42,20 +28,12 @@ def test_warp_frame_example_builds(tmp_path):
 
 
 def test_cli_argument_errors(tmp_path):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    for args in ([], ["a.npy"], ["a.npy", "b.npy", "c.flo"], ["a.npy", "b.npy", "c.flo", "d.png", "--fill", "x"],
-                 ["a.npy", "b.npy", "c.flo", "d.png", "--occ"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.warp_frame"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
-        assert r.returncode != 0 and "usage" in r.stderr, args
+    cli_refuses("warp_frame", ([], ["a.npy"], ["a.npy", "b.npy", "c.flo"], ["a.npy", "b.npy", "c.flo", "d.png", "--fill", "x"],
+                               ["a.npy", "b.npy", "c.flo", "d.png", "--occ"]))
 
 
 def test_resource_table_lists_the_warp_kernels_without_scratch():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "flowonthego_amd", "csrc")], stdout=subprocess.DEVNULL)
-    txt = open(os.path.join(ROOT, "flowonthego_amd", "libfotg.resusage.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", txt)]
-    assert len(names) == len(scratch)
-    table = dict(zip(names, scratch))
+    names, table = resource_table()
     # Src x element type x channels, Itanium-mangled: warp_kernel<DenseSrc | UpsampleSrc, float | unsigned char, 1 | 3>
     for src in ("NS_8DenseSrcE", "NS_11UpsampleSrcE"):
         for t in ("f", "h"):
