@@ -53,9 +53,12 @@ def __getattr__(name):
     if name in ("upsample_crop_motion_histograms", "motion_descriptors", "HIST"):
         from . import histograms
         return getattr(histograms, name)
-    if name in ("fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms"):
+    if name in ("upsample_crop_motion_blur", "BLUR_STATS"):
+        from . import motionblur
+        return getattr(motionblur, "STATS" if name == "BLUR_STATS" else name)
+    if name in ("fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms", "motion_blur"):
         # (the command-line modules of these names; each is callable as the function of flowonthego_amd.motion / objects / tracks /
-        # histograms)
+        # histograms / motionblur)
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("interpolate", "upsample_crop_interpolate"):

@@ -352,6 +352,19 @@ class OFClass:
                                      fit_thresh=fit_thresh, min_area=min_area, max_objects=max_objects, connectivity=connectivity,
                                      cells=cells)
 
+    def upsample_crop_motion_blur(self, flow, frame, mask=None, shutter=0.5, max_blur=32, code=False, vectors=False, stats=False, fused=True):
+        """frame blurred along upsample_crop(flow), a shutter simulated per frame; fused: the full-resolution flow is never written --
+        flowonthego_amd.motionblur"""
+        from .motionblur import upsample_crop_motion_blur
+        return upsample_crop_motion_blur(self, flow, frame, mask=mask, shutter=shutter, max_blur=max_blur, code=code, vectors=vectors,
+                                         stats=stats, fused=fused)
+
+    def motion_blur(self, frames, shutter=0.5, max_blur=32, occlusion=False):
+        """frames (T+1, ...) -> frames 0 .. T-1 blurred along their forward flows, in chunks of max_batch; with occlusion (a bidir
+        context) the consistency mask says which vectors are unknown -- flowonthego_amd.motionblur"""
+        from .motionblur import ofc_motion_blur
+        return ofc_motion_blur(self, frames, shutter=shutter, max_blur=max_blur, occlusion=occlusion)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

@@ -784,6 +784,51 @@ int fotg_upsample_crop_motion_histograms(fotg_ctx *ctx, int n, const float *coar
                                          int cell, int thresh256, long long *cells, const int *ids, int rows, long long *objects,
                                          void *stream);
 
+/* ---- motion blur along a flow: a shutter simulated per frame, csrc/motionblur.hip.h ------------------------------------------------
+ * Blurs a frame along its flow: the tile-max / neighbour-max scatter-as-gather reconstruction filter (McGuire et al. 2012, the
+ * direction test of Guertin et al. 2014, both without depth).  A static pixel is untouched unless something within reach moves
+ * across it; a moving object smears over its surroundings by its own half-streak; a fast pixel moving across the line does not
+ * smear along it.  One f32 multiply per component, integers after it; lengths in 1/16 pixel.  Inputs: src, n x h x w x channels,
+ * 8-bit (type FOTG_BLUR_U8) or f32 (FOTG_BLUR_F32), channels 1 or 3; flow, n x h x w x 2 f32, the flow of src's frame; mask, NULL
+ * or n x h x w uint8 in the alphabet of fotg_fb_check.  The definition, in order:
+ *   1. Half-vector.  shutter256 in 1 .. 512 is round(256 shutter) (shutter 1 = the exposure lasts the whole frame interval);
+ *      s = (float)shutter256 / 32 (exact); hx = (int)rintf(u s), hy = (int)rintf(v s).  A pixel is unknown, H = (0, 0), when u or v
+ *      is not finite or |u| or |v| is above 4096, or a mask is given and its byte is non-zero.  len = M(hx, hy), the exact integer
+ *      root of the motion histograms (step 3 there); cap16 = 16 max_blur, max_blur in 1 .. 32 pixels; if len > cap16 then
+ *      hx = hx cap16 / len, hy = hy cap16 / len (C integer division: towards zero) and len = M(hx, hy) again.
+ *   2. Tiles of 32 x 32 pixels, partial at the right and bottom edges.  tilemax = the H of the tile's pixel with the largest
+ *      hx hx + hy hy, the lowest linear pixel index on a tie.  D(tile) = the tilemax with the largest squared length among the up to
+ *      nine tiles around it, the first in raster order on a tie.  lenD = M(Dx, Dy).
+ *   3. Gather, for the pixel X = (x, y) of a tile with D.  lenD < 8: dst = src, code 0, or 3 if X is unknown (the copy path).
+ *      Otherwise L = (lenD + 15) / 16 (at most 32) and for k = -L .. L, with a = |k|:
+ *        o_k = (ox, oy): ox = sign(Dx k) ((2 |Dx| a + L) / (2 L)), oy alike (half away from zero: o_-k = -o_k)
+ *        Y_k = (x + ((ox + 8) >> 4), y + ((oy + 8) >> 4)) (arithmetic shift: the nearest pixel, a half towards +inf), clamped to
+ *              the frame; the tap is `clamped` when the clamp moved it
+ *        d_k = lenD a / L
+ *        r(P) = |Hx(P) Dx + Hy(P) Dy| / lenD                                   (integer division: the reach of P along the line)
+ *        w_k = clamp(max(r(Y_k), r(X)) + 16 - d_k, 0, 16)                        (so w_0 = 16)
+ *      8-bit frames, per channel: dst = (2 sum w_k c_k + W) / (2 W), W = sum w_k, in integers.  f32 frames: acc = 0, then
+ *      acc = acc + (float)w_k c_k for k ascending, every tap (those of weight 0 too), every operation rounded on its own;
+ *      dst = acc / (float)W.
+ *      code = the first that applies of: 3, X is unknown; 2, a tap with w_k > 0 was clamped; 1, a tap k != 0 had w_k > 0; 0.
+ *   4. stats, per image eight int64: the pixels of code 0, 1, 2, 3; the taps with w_k > 0 summed over the pixels of the gather
+ *      path (k = 0 included; a pixel of the copy path adds none); the tiles that took the copy path; the largest len; 0.
+ * Outputs: dst, of src's shape and type; code, NULL or n x h x w uint8; vectors, NULL or n x h x w x 2 int16, H; stats, NULL or
+ * n x 8 int64.  Two identical calls give identical bytes.  Everything is enqueued on `stream`; H and the tile maxima live in
+ * stream-ordered memory of the call.  FOTG_ERR_ARG, decided before the device is touched: n outside 1 .. 65535, w or h outside
+ * 1 .. 16384, a type or channel count that is none of the above, shutter256 outside 1 .. 512, max_blur outside 1 .. 32, a null src,
+ * flow or dst, an output overlapping an input or another output. */
+enum { FOTG_BLUR_U8 = 0, FOTG_BLUR_F32 = 1 };
+int fotg_motion_blur(int device, int n, const void *src, int type, int channels, const float *flow, int w, int h,
+                     const unsigned char *mask, int shutter256, int max_blur, void *dst, unsigned char *code, short *vectors,
+                     long long *stats, void *stream);
+/* The same on the coarse flow of a context (n x hl x wl x 2, as fotg_calc_batch returns it), upsampled and cropped on the fly, src
+ * and mask of h_org x w_org: every output equals fotg_motion_blur on fotg_upsample_crop's output bit for bit, without the
+ * full-resolution flow ever being written.  FOTG_ERR_ARG also for n > max_batch and a depth-mode context. */
+int fotg_upsample_crop_motion_blur(fotg_ctx *ctx, int n, const void *src, int type, int channels, const float *coarse_flow,
+                                   const unsigned char *mask, int shutter256, int max_blur, void *dst, unsigned char *code,
+                                   short *vectors, long long *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
