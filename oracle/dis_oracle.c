@@ -28,6 +28,21 @@
 #include <time.h>
 #include "dis_oracle.h"
 
+/* math calls on dis_real (dis_oracle.h): the f32 forms in the default build, the double forms under -DDIS_REAL_DOUBLE */
+#ifdef DIS_REAL_DOUBLE
+#define DIS_SQRT sqrt
+#define DIS_FABS fabs
+#define DIS_COPYSIGN copysign
+#define DIS_FLOOR floor
+#else
+#define DIS_SQRT sqrtf
+#define DIS_FABS fabsf
+#define DIS_COPYSIGN copysignf
+#define DIS_FLOOR floorf
+#endif
+/* a parameter derived from others is computed in f32 in both builds (no-op casts in the default one), then widened */
+#define DIS_F32(x) ((float)(x))
+
 /* ------------------------------------------------------------------------------------------- */
 /* allocation: every buffer of the port goes through dis_alloc / dis_release.  Outside          */
 /* dis_flow_many() they are malloc / free.  Inside it every worker thread keeps the blocks it    */
@@ -123,7 +138,7 @@ void dis_padded_size(int w, int h, int sc_f, int *wp, int *hp, int *padw, int *p
 }
 
 /* kroeger/run_dense.cpp:306-310: copyMakeBorder(top=floor(padh/2), bottom=ceil, left=floor(padw/2), right=ceil, REPLICATE) */
-void dis_pad_frame(const float *in, int w, int h, int noc, int sc_f, float *out)
+void dis_pad_frame(const dis_real *in, int w, int h, int noc, int sc_f, dis_real *out)
 {
   int wp, hp, padw, padh;
   dis_padded_size(w, h, sc_f, &wp, &hp, &padw, &padh);
@@ -140,17 +155,17 @@ void dis_pad_frame(const float *in, int w, int h, int noc, int sc_f, float *out)
 /* kroeger/run_dense.cpp:138-147 (the SELECTCHANNEL==2 build): the pyramid's level 0 is the gradient magnitude of the padded
  * frame -- cv::Sobel(ksize 1, BORDER_DEFAULT) = I(x+1) - I(x-1) / I(y+1) - I(y-1) per channel with REFLECT_101 at the frame's
  * edge (index -1 -> 1, n -> n-2), then sqrt(dx*dx + dy*dy), all in f32.  in / out: w x h x noc, w, h >= 2. */
-void dis_gradient_magnitude(const float *in, int w, int h, int noc, float *out)
+void dis_gradient_magnitude(const dis_real *in, int w, int h, int noc, dis_real *out)
 {
   for (int y = 0; y < h; ++y) {
     int ym = y > 0 ? y - 1 : 1, yp = y < h - 1 ? y + 1 : h - 2;
     for (int x = 0; x < w; ++x) {
       int xm = x > 0 ? x - 1 : 1, xp = x < w - 1 ? x + 1 : w - 2;
       for (int c = 0; c < noc; ++c) {
-        float dx = in[((size_t)y * w + xp) * noc + c] - in[((size_t)y * w + xm) * noc + c];
-        float dy = in[((size_t)yp * w + x) * noc + c] - in[((size_t)ym * w + x) * noc + c];
-        float dx2 = dx * dx, dy2 = dy * dy;
-        out[((size_t)y * w + x) * noc + c] = sqrtf(dx2 + dy2);
+        dis_real dx = in[((size_t)y * w + xp) * noc + c] - in[((size_t)y * w + xm) * noc + c];
+        dis_real dy = in[((size_t)yp * w + x) * noc + c] - in[((size_t)ym * w + x) * noc + c];
+        dis_real dx2 = dx * dx, dy2 = dy * dy;
+        out[((size_t)y * w + x) * noc + c] = DIS_SQRT(dx2 + dy2);
       }
     }
   }
@@ -165,26 +180,26 @@ int dis_level_h(const dis_pyramid *p, int l) { return p->h0 >> l; }
 
 static int reflect101(int i, int n) { if (i < 0) return -i; if (i >= n) return 2 * n - 2 - i; return i; }
 
-dis_pyramid *dis_pyramid_build(const float *img, int wp, int hp, int noc, int sc_f, int ps)
+dis_pyramid *dis_pyramid_build(const dis_real *img, int wp, int hp, int noc, int sc_f, int ps)
 {
   dis_pyramid *P = (dis_pyramid *)calloc(1, sizeof(dis_pyramid));
   P->nlev = sc_f + 1; P->noc = noc; P->ps = ps; P->w0 = wp; P->h0 = hp;
-  P->im = (float **)calloc(P->nlev, sizeof(float *));
-  P->dx = (float **)calloc(P->nlev, sizeof(float *));
-  P->dy = (float **)calloc(P->nlev, sizeof(float *));
-  float *prev = NULL; int pw = 0;
+  P->im = (dis_real **)calloc(P->nlev, sizeof(dis_real *));
+  P->dx = (dis_real **)calloc(P->nlev, sizeof(dis_real *));
+  P->dy = (dis_real **)calloc(P->nlev, sizeof(dis_real *));
+  dis_real *prev = NULL; int pw = 0;
   for (int l = 0; l <= sc_f; ++l) {
     int w = wp >> l, h = hp >> l;
-    float *cur = (float *)malloc(sizeof(float) * (size_t)w * h * noc);
-    if (l == 0) memcpy(cur, img, sizeof(float) * (size_t)w * h * noc);       /* :137 clone */
+    dis_real *cur = (dis_real *)malloc(sizeof(dis_real) * (size_t)w * h * noc);
+    if (l == 0) memcpy(cur, img, sizeof(dis_real) * (size_t)w * h * noc);       /* :137 clone */
     else {
       /* :150 cv::resize(.5,.5,INTER_LINEAR) == exact 2x2 mean (OpenCV maps it to INTER_AREA) */
       for (int y = 0; y < h; ++y) for (int x = 0; x < w; ++x) for (int c = 0; c < noc; ++c) {
-        const float a = prev[((size_t)(2 * y) * pw + 2 * x) * noc + c];
-        const float b = prev[((size_t)(2 * y) * pw + 2 * x + 1) * noc + c];
-        const float cc = prev[((size_t)(2 * y + 1) * pw + 2 * x) * noc + c];
-        const float d = prev[((size_t)(2 * y + 1) * pw + 2 * x + 1) * noc + c];
-        float m;
+        const dis_real a = prev[((size_t)(2 * y) * pw + 2 * x) * noc + c];
+        const dis_real b = prev[((size_t)(2 * y) * pw + 2 * x + 1) * noc + c];
+        const dis_real cc = prev[((size_t)(2 * y + 1) * pw + 2 * x) * noc + c];
+        const dis_real d = prev[((size_t)(2 * y + 1) * pw + 2 * x + 1) * noc + c];
+        dis_real m;
         switch (g_mean_order) {
           case 1: m = ((a + b) + (cc + d)) * 0.25f; break;
           case 2: m = (((a + b) + cc) + d) * 0.25f; break;
@@ -196,9 +211,9 @@ dis_pyramid *dis_pyramid_build(const float *img, int wp, int hp, int noc, int sc
     }
     /* :156-157 Sobel ksize=1 -> [-1 0 1], BORDER_DEFAULT = REFLECT_101; :166-175 pad */
     int tw = w + 2 * ps, th = h + 2 * ps;
-    float *pim = (float *)malloc(sizeof(float) * (size_t)tw * th * noc);
-    float *pdx = (float *)calloc((size_t)tw * th * noc, sizeof(float));
-    float *pdy = (float *)calloc((size_t)tw * th * noc, sizeof(float));
+    dis_real *pim = (dis_real *)malloc(sizeof(dis_real) * (size_t)tw * th * noc);
+    dis_real *pdx = (dis_real *)calloc((size_t)tw * th * noc, sizeof(dis_real));
+    dis_real *pdy = (dis_real *)calloc((size_t)tw * th * noc, sizeof(dis_real));
     for (int y = 0; y < th; ++y) {
       int sy = y - ps; if (sy < 0) sy = 0; if (sy > h - 1) sy = h - 1;
       for (int x = 0; x < tw; ++x) {
@@ -231,17 +246,17 @@ void dis_pyramid_free(dis_pyramid *p)
 /* reductions (definition D1)                                                                  */
 /* ------------------------------------------------------------------------------------------- */
 
-static float dis_sum_pairwise(const float *v, int n)
+static dis_real dis_sum_pairwise(const dis_real *v, int n)
 {
   if (n <= 2) return n == 2 ? v[0] + v[1] : v[0];
   const int h = n / 2;
   return dis_sum_pairwise(v, h) + dis_sum_pairwise(v + h, n - h);
 }
 
-float dis_sum(const float *v, int n, int noc)
+dis_real dis_sum(const dis_real *v, int n, int noc)
 {
   if (g_sum_order == 1) {                       /* sequential, the order of a scalar loop */
-    float acc = v[0];
+    dis_real acc = v[0];
     for (int e = 1; e < n; ++e) acc = acc + v[e];
     return acc;
   }
@@ -249,39 +264,39 @@ float dis_sum(const float *v, int n, int noc)
     /* Eigen-style vectorised redux with 4-float packets (SSE, the reference's -msse4 build; Eigen 3.3 Core/Redux.h,
      * LinearVectorizedTraversal): two packet accumulators over alternating packets, added; then a trailing odd packet; then
      * the horizontal sum (a0 + a2) + (a1 + a3) (movehl / shuffle form of predux); then the scalar tail */
-    if (n < 4) { float r = v[0]; for (int e = 1; e < n; ++e) r = r + v[e]; return r; }
+    if (n < 4) { dis_real r = v[0]; for (int e = 1; e < n; ++e) r = r + v[e]; return r; }
     const int al2 = (n / 8) * 8, al = (n / 4) * 4;
-    float q[4];
+    dis_real q[4];
     for (int k = 0; k < 4; ++k) q[k] = v[k];
     if (al > 4) {
-      float p1[4];
+      dis_real p1[4];
       for (int k = 0; k < 4; ++k) p1[k] = v[4 + k];
       for (int e = 8; e < al2; e += 8) for (int k = 0; k < 4; ++k) { q[k] = q[k] + v[e + k]; p1[k] = p1[k] + v[e + 4 + k]; }
       for (int k = 0; k < 4; ++k) q[k] = q[k] + p1[k];
       if (al > al2) for (int k = 0; k < 4; ++k) q[k] = q[k] + v[al2 + k];
     }
-    float r = (q[0] + q[2]) + (q[1] + q[3]);
+    dis_real r = (q[0] + q[2]) + (q[1] + q[3]);
     for (int e = al; e < n; ++e) r = r + v[e];
     return r;
   }
   if (g_sum_order == 3) return dis_sum_pairwise(v, n);
   /* 16 partial sums: pixel q (element e / noc) goes to partial q % 16, elements in ascending order; then the balanced
    * tree over the 16 partials (xor 8, 4, 2, 1).  Every supported patch has a multiple of 16 pixels. */
-  float lane[16]; int used[16];
+  dis_real lane[16]; int used[16];
   for (int i = 0; i < 16; ++i) { lane[i] = 0.0f; used[i] = 0; }
   for (int e = 0; e < n; ++e) {
     int l = (e / noc) & 15;
     if (!used[l]) { lane[l] = v[e]; used[l] = 1; } else lane[l] = lane[l] + v[e];
   }
   for (int k = 8; k >= 1; k >>= 1) {
-    float t[16];
+    dis_real t[16];
     for (int i = 0; i < 16; ++i) t[i] = lane[i] + lane[i ^ k];
     memcpy(lane, t, sizeof(t));
   }
   return lane[0];
 }
 
-static float dis_dot(const float *a, const float *b, int n, int noc, float *scratch)
+static dis_real dis_dot(const dis_real *a, const dis_real *b, int n, int noc, dis_real *scratch)
 {
   for (int i = 0; i < n; ++i) scratch[i] = a[i] * b[i];
   return dis_sum(scratch, n, noc);
@@ -297,31 +312,31 @@ dis_grid *dis_grid_new(int w, int h, int lvl, const dis_params *p)
   dis_grid *g = (dis_grid *)calloc(1, sizeof(dis_grid));
   g->w = w; g->h = h; g->ps = p->ps; g->noc = p->noc; g->lvl = lvl;
   g->depth = p->depth; g->camlr = 0;
-  int steps = (int)floor(p->ps * (1 - p->patove));               /* oflow.cpp:91 */
+  int steps = (int)floor((float)p->ps * (1.0f - DIS_F32(p->patove)));   /* oflow.cpp:91 */
   g->steps = steps > 1 ? steps : 1;
   g->pad = p->ps; g->tmp_w = w + 2 * p->ps;
-  g->lb = -(float)p->ps / 2;                                       /* oflow.cpp:147 */
-  g->ubw = (float)(w + p->ps / 2 - 2);                             /* :148 */
-  g->ubh = (float)(h + p->ps / 2 - 2);                             /* :149 */
+  g->lb = -(dis_real)p->ps / 2;                                       /* oflow.cpp:147 */
+  g->ubw = (dis_real)(w + p->ps / 2 - 2);                             /* :148 */
+  g->ubh = (dis_real)(h + p->ps / 2 - 2);                             /* :149 */
   g->nopw = (int)ceil((float)w / (float)g->steps);                 /* patchgrid.cpp:43 */
   g->noph = (int)ceil((float)h / (float)g->steps);
   const int offw = (int)floor((w - (g->nopw - 1) * g->steps) / 2); /* :45 (integer division) */
   const int offh = (int)floor((h - (g->noph - 1) * g->steps) / 2);
   g->nop = g->nopw * g->noph;
   int nv = p->ps * p->ps * p->noc;
-  g->pt_ref = (float *)calloc((size_t)g->nop * 2, sizeof(float));
-  g->p_init = (float *)calloc((size_t)g->nop * 2, sizeof(float));
-  g->p_iter = (float *)calloc((size_t)g->nop * 2, sizeof(float));
-  g->tmpl = (float *)calloc((size_t)g->nop * nv, sizeof(float));
-  g->tdx = (float *)calloc((size_t)g->nop * nv, sizeof(float));
-  g->tdy = (float *)calloc((size_t)g->nop * nv, sizeof(float));
-  g->pweight = (float *)calloc((size_t)g->nop * nv, sizeof(float));
-  g->hes = (float *)calloc((size_t)g->nop * 3, sizeof(float));
+  g->pt_ref = (dis_real *)calloc((size_t)g->nop * 2, sizeof(dis_real));
+  g->p_init = (dis_real *)calloc((size_t)g->nop * 2, sizeof(dis_real));
+  g->p_iter = (dis_real *)calloc((size_t)g->nop * 2, sizeof(dis_real));
+  g->tmpl = (dis_real *)calloc((size_t)g->nop * nv, sizeof(dis_real));
+  g->tdx = (dis_real *)calloc((size_t)g->nop * nv, sizeof(dis_real));
+  g->tdy = (dis_real *)calloc((size_t)g->nop * nv, sizeof(dis_real));
+  g->pweight = (dis_real *)calloc((size_t)g->nop * nv, sizeof(dis_real));
+  g->hes = (dis_real *)calloc((size_t)g->nop * 3, sizeof(dis_real));
   g->cnt = (int *)calloc((size_t)g->nop, sizeof(int));
   for (int x = 0; x < g->nopw; ++x) for (int y = 0; y < g->noph; ++y) {
     int i = x * g->noph + y;                                       /* :66 column-major ids */
-    g->pt_ref[2 * i] = (float)(x * g->steps + offw);
-    g->pt_ref[2 * i + 1] = (float)(y * g->steps + offh);
+    g->pt_ref[2 * i] = (dis_real)(x * g->steps + offw);
+    g->pt_ref[2 * i + 1] = (dis_real)(y * g->steps + offh);
   }
   return g;
 }
@@ -334,12 +349,12 @@ void dis_grid_free(dis_grid *g)
 }
 
 /* patchgrid.cpp:98-116 -> patch.cpp:57-69 InitializePatch; :287-332 getPatchStaticNNGrad; :71-88 ComputeHessian */
-void dis_grid_init(dis_grid *g, const dis_params *p, const float *I0, const float *I0x, const float *I0y)
+void dis_grid_init(dis_grid *g, const dis_params *p, const dis_real *I0, const dis_real *I0x, const dis_real *I0y)
 {
   const int ps = g->ps, noc = g->noc, nv = ps * ps * noc;
-  float *scr = (float *)malloc(sizeof(float) * nv);
+  dis_real *scr = (dis_real *)malloc(sizeof(dis_real) * nv);
   for (int ip = 0; ip < g->nop; ++ip) {
-    float *T = g->tmpl + (size_t)ip * nv, *Tx = g->tdx + (size_t)ip * nv, *Ty = g->tdy + (size_t)ip * nv;
+    dis_real *T = g->tmpl + (size_t)ip * nv, *Tx = g->tdx + (size_t)ip * nv, *Ty = g->tdy + (size_t)ip * nv;
     int px = (int)round(g->pt_ref[2 * ip]) + g->pad;
     int py = (int)round(g->pt_ref[2 * ip + 1]) + g->pad;
     int lb = -ps / 2, ub = ps / 2 - 1, k = 0;
@@ -348,11 +363,11 @@ void dis_grid_init(dis_grid *g, const dis_params *p, const float *I0, const floa
       for (int c = 0; c < noc; ++c, ++k) { T[k] = I0[idx + c]; Tx[k] = I0x[idx + c]; Ty[k] = I0y[idx + c]; }
     }
     if (p->patnorm > 0) {                                           /* patch.cpp:330-331 */
-      float m = dis_sum(T, nv, noc) / nv;
+      dis_real m = dis_sum(T, nv, noc) / nv;
       for (int e = 0; e < nv; ++e) T[e] -= m;
     }
-    float h00 = dis_dot(Tx, Tx, nv, noc, scr);                      /* patch.cpp:74-77 */
-    float h01 = 0.0f, h11 = 0.0f;
+    dis_real h00 = dis_dot(Tx, Tx, nv, noc, scr);                      /* patch.cpp:74-77 */
+    dis_real h01 = 0.0f, h11 = 0.0f;
     if (g->depth) {                                                 /* :83-87: 1x1 Hessian */
       if (h00 == 0) h00 += 1e-10;
     } else {
@@ -367,7 +382,7 @@ void dis_grid_init(dis_grid *g, const dis_params *p, const float *I0, const floa
 }
 
 /* patchgrid.cpp:195-211 */
-void dis_grid_init_from_coarser(dis_grid *g, const float *flow_prev)
+void dis_grid_init_from_coarser(dis_grid *g, const dis_real *flow_prev)
 {
   for (int ip = 0; ip < g->nop; ++ip) {
     int x = (int)floor(g->pt_ref[2 * ip] / 2);
@@ -385,27 +400,30 @@ void dis_grid_init_from_coarser(dis_grid *g, const float *flow_prev)
 }
 
 /* patch.cpp:335-402 getPatchStaticBil (+ mean normalisation :400-401) */
-static void patch_bil(const dis_grid *g, const dis_params *p, const float *img, float mx, float my, float *out)
+static void patch_bil(const dis_grid *g, const dis_params *p, const dis_real *img, dis_real mx, dis_real my, dis_real *out)
 {
   const int ps = g->ps, noc = g->noc, nv = ps * ps * noc;
-  int pos0 = (int)ceil(mx + .00001f), pos1 = (int)ceil(my + .00001f);
+  /* the corner rule is an integer decision and belongs to the problem, not to its rounding: the position is taken in f32 in both
+     builds (a no-op in the default one).  In f32 the 1e-5 is absorbed from 256 on (half an ulp there is 1.5e-5), so an integer
+     position >= 256 keeps pos0 == pos2 and the patch samples one pixel to the left; in double it would not be. */
+  int pos0 = (int)ceil(DIS_F32(mx) + .00001f), pos1 = (int)ceil(DIS_F32(my) + .00001f);
   int pos2 = (int)floor(mx), pos3 = (int)floor(my);
-  float r0 = mx - (float)pos2, r1 = my - (float)pos3;
-  float we0 = r0 * r1, we1 = (1 - r0) * r1, we2 = r0 * (1 - r1), we3 = (1 - r0) * (1 - r1);
+  dis_real r0 = mx - (dis_real)pos2, r1 = my - (dis_real)pos3;
+  dis_real we0 = r0 * r1, we1 = (1 - r0) * r1, we2 = r0 * (1 - r1), we3 = (1 - r0) * (1 - r1);
   pos0 += g->pad; pos1 += g->pad;
   int lb = -ps / 2, ub = ps / 2 - 1, k = 0;
   for (int yy = pos1 + lb; yy <= pos1 + ub; ++yy) {
     for (int xx = pos0 + lb; xx <= pos0 + ub; ++xx) {
-      const float *a = img + ((size_t)yy * g->tmp_w + xx) * noc;
-      const float *b = a - noc;
-      const float *c = img + ((size_t)(yy - 1) * g->tmp_w + xx) * noc;
-      const float *d = c - noc;
+      const dis_real *a = img + ((size_t)yy * g->tmp_w + xx) * noc;
+      const dis_real *b = a - noc;
+      const dis_real *c = img + ((size_t)(yy - 1) * g->tmp_w + xx) * noc;
+      const dis_real *d = c - noc;
       for (int ch = 0; ch < noc; ++ch, ++k)
         out[k] = we0 * a[ch] + we1 * b[ch] + we2 * c[ch] + we3 * d[ch];
     }
   }
   if (p->patnorm > 0) {
-    float m = dis_sum(out, nv, noc) / nv;
+    dis_real m = dis_sum(out, nv, noc) / nv;
     for (int e = 0; e < nv; ++e) out[e] -= m;
   }
 }
@@ -417,36 +435,36 @@ static void patch_bil(const dis_grid *g, const dis_params *p, const float *img, 
  *   h11 - l10^2 <= 0:      L = [sqrt(h00) 0; l10 h11]
  * A NaN pivot is not <= 0 and goes through sqrt.  The second case is every rank-deficient patch whose Hessian the
  * determinant test (:78-82) lifts by only 1e-10: linear ramps, straight edges, one-directional texture. */
-static inline float dis_llt_diag(float x) { return x <= 0.0f ? x : sqrtf(x); }
-static inline void dis_llt2(float h00, float h01, float h11, float *l00, float *l10, float *l11)
+static inline dis_real dis_llt_diag(dis_real x) { return x <= 0.0f ? x : DIS_SQRT(x); }
+static inline void dis_llt2(dis_real h00, dis_real h01, dis_real h11, dis_real *l00, dis_real *l10, dis_real *l11)
 {
   if (h00 <= 0.0f) { *l00 = h00; *l10 = h01; *l11 = h11; return; }
-  *l00 = sqrtf(h00);
+  *l00 = DIS_SQRT(h00);
   *l10 = h01 / *l00;
-  const float x = h11 - *l10 * *l10;
-  *l11 = x <= 0.0f ? h11 : sqrtf(x);
+  const dis_real x = h11 - *l10 * *l10;
+  *l11 = x <= 0.0f ? h11 : DIS_SQRT(x);
 }
 
 /* patchgrid.cpp:134-141 Optimize -> patch.cpp:159-212 OptimizeIter, :120-156 OptimizeStart,
  * :264-284 OptimizeComputeErrImg, :223-261 LossComputeErrorImage (costfct 0 L2, 1 L1, 2 pseudo-Huber) */
-void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float *trace)
+void dis_grid_optimize(dis_grid *g, const dis_params *p, const dis_real *I1, dis_real *trace)
 {
   const int ps = g->ps, noc = g->noc, nv = ps * ps * noc;
-  const float dp_thresh = p->dp_thresh * p->dp_thresh;               /* oflow.cpp:88 */
-  const float outlier = (float)ps / 2;                               /* oflow.cpp:82 */
-  float *pdiff = (float *)malloc(sizeof(float) * nv), *scr = (float *)malloc(sizeof(float) * nv);
+  const dis_real dp_thresh = DIS_F32(p->dp_thresh) * DIS_F32(p->dp_thresh);   /* oflow.cpp:88 */
+  const dis_real outlier = (dis_real)ps / 2;                               /* oflow.cpp:82 */
+  dis_real *pdiff = (dis_real *)malloc(sizeof(dis_real) * nv), *scr = (dis_real *)malloc(sizeof(dis_real) * nv);
   const int trow = p->max_iter + 1;
   for (int ip = 0; ip < g->nop; ++ip) {
-    const float *T = g->tmpl + (size_t)ip * nv, *Tx = g->tdx + (size_t)ip * nv, *Ty = g->tdy + (size_t)ip * nv;
-    float *pw = g->pweight + (size_t)ip * nv;
-    const float h00 = g->hes[3 * ip], h01 = g->hes[3 * ip + 1], h11 = g->hes[3 * ip + 2];
-    const float rx = g->pt_ref[2 * ip], ry = g->pt_ref[2 * ip + 1];
-    const float pin0 = g->p_init[2 * ip], pin1 = g->p_init[2 * ip + 1];
-    float p0 = pin0, p1 = pin1;
-    float ptx = rx + p0, pty = ry + p1;                              /* paramtopt :214-221 */
-    const float stx = ptx, sty = pty;
+    const dis_real *T = g->tmpl + (size_t)ip * nv, *Tx = g->tdx + (size_t)ip * nv, *Ty = g->tdy + (size_t)ip * nv;
+    dis_real *pw = g->pweight + (size_t)ip * nv;
+    const dis_real h00 = g->hes[3 * ip], h01 = g->hes[3 * ip + 1], h11 = g->hes[3 * ip + 2];
+    const dis_real rx = g->pt_ref[2 * ip], ry = g->pt_ref[2 * ip + 1];
+    const dis_real pin0 = g->p_init[2 * ip], pin1 = g->p_init[2 * ip + 1];
+    dis_real p0 = pin0, p1 = pin1;
+    dis_real ptx = rx + p0, pty = ry + p1;                              /* paramtopt :214-221 */
+    const dis_real stx = ptx, sty = pty;
     int conv = 0, cnt = 0;
-    float dp0 = 0, dp1 = 0, dpn = 1e-10f, dpn_init = 1e-10f, mares = 1e20f, mares_old = 1e20f;
+    dis_real dp0 = 0, dp1 = 0, dpn = 1e-10f, dpn_init = 1e-10f, mares = 1e20f, mares_old = 1e20f;
     if (trace) for (int t = 0; t < trow * 4; ++t) trace[((size_t)ip * trow) * 4 + t] = 0;
     if (ptx < g->lb || pty < g->lb || ptx > g->ubw || pty > g->ubh) {   /* :135-141 */
       conv = 1;
@@ -459,18 +477,18 @@ void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float 
       cnt++;
       dp0 = dis_dot(Tx, pdiff, nv, noc, scr);                        /* :178-179 */
       if (g->depth) {                                                /* :181, :184 with the 1x1 Hessian: L = sqrt(H) */
-        float l00 = dis_llt_diag(h00);
-        float y0 = dp0 / l00;
+        dis_real l00 = dis_llt_diag(h00);
+        dis_real y0 = dp0 / l00;
         dp0 = y0 / l00; dp1 = 0.0f;
       } else {
       dp1 = dis_dot(Ty, pdiff, nv, noc, scr);
       {                                                              /* :184 Hes.llt().solve() (Eigen LLT, see dis_llt2) */
-        float l00, l10, l11;
+        dis_real l00, l10, l11;
         dis_llt2(h00, h01, h11, &l00, &l10, &l11);
-        float y0 = dp0 / l00;
-        float y1 = (dp1 - l10 * y0) / l11;
-        float x1 = y1 / l11;
-        float x0 = (y0 - l10 * x1) / l00;
+        dis_real y0 = dp0 / l00;
+        dis_real y1 = (dp1 - l10 * y0) / l11;
+        dis_real x1 = y1 / l11;
+        dis_real x0 = (y0 - l10 * x1) / l00;
         dp0 = x0; dp1 = x1;
       }
       }
@@ -481,9 +499,9 @@ void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float 
       }
       ptx = rx + p0; pty = ry + p1;
       {
-        float ddx = stx - ptx, ddy = sty - pty;
+        dis_real ddx = stx - ptx, ddy = sty - pty;
         int bad = !(isfinite(dp0) && isfinite(dp1));                 /* (D3): only non-finite input data gets here */
-        if (bad || sqrtf(ddx * ddx + ddy * ddy) > outlier ||         /* :199-208 */
+        if (bad || DIS_SQRT(ddx * ddx + ddy * ddy) > outlier ||         /* :199-208 */
             ptx < g->lb || pty < g->lb || ptx > g->ubw || pty > g->ubh) {
           p0 = pin0; p1 = pin1; ptx = rx + p0; pty = ry + p1;
           conv = 1;
@@ -493,13 +511,13 @@ void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float 
     compute_err:
       patch_bil(g, p, I1, ptx, pty, pdiff);                          /* :266 */
       for (int e = 0; e < nv; ++e) {
-        float d = pdiff[e] - T[e];                                   /* :230-236 L2: the difference image itself */
-        if (p->costfct == 1) d = copysignf(sqrtf(fabsf(d)), d);      /* :238-246 L1: sign(d) * sqrt(|d|) */
+        dis_real d = pdiff[e] - T[e];                                   /* :230-236 L2: the difference image itself */
+        if (p->costfct == 1) d = DIS_COPYSIGN(DIS_SQRT(DIS_FABS(d)), d);      /* :238-246 L1: sign(d) * sqrt(|d|) */
         else if (p->costfct == 2) {                                  /* :247-261 pseudo-Huber, b = normoutlier (oflow.cpp:106-107) */
-          const float bsq = p->normoutlier * p->normoutlier, bsq2 = bsq * 2.0f;
-          d = copysignf(sqrtf((sqrtf(1.0f + (d * d) / bsq) - 1.0f) * bsq2), d);
+          const float bsq = DIS_F32(p->normoutlier) * DIS_F32(p->normoutlier), bsq2 = bsq * 2.0f;
+          d = DIS_COPYSIGN(DIS_SQRT((DIS_SQRT(1.0f + (d * d) / bsq) - 1.0f) * bsq2), d);
         }
-        pdiff[e] = d; pw[e] = fabsf(d);
+        pdiff[e] = d; pw[e] = DIS_FABS(d);
       }
       dpn = dp0 * dp0 + dp1 * dp1;                                   /* :272 */
       if (cnt == 1) dpn_init = dpn;
@@ -510,8 +528,8 @@ void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float 
             ((cnt < p->min_iter) | (mares / mares_old <= p->dr_thresh))))
         conv = 1;
       if (trace && cnt <= p->max_iter) {
-        float *tr = trace + ((size_t)ip * trow + cnt) * 4;
-        tr[0] = p0; tr[1] = p1; tr[2] = mares; tr[3] = (float)cnt;
+        dis_real *tr = trace + ((size_t)ip * trow + cnt) * 4;
+        tr[0] = p0; tr[1] = p1; tr[2] = mares; tr[3] = (dis_real)cnt;
       }
     }
     g->p_iter[2 * ip] = p0; g->p_iter[2 * ip + 1] = p1; g->cnt[ip] = cnt;
@@ -520,36 +538,36 @@ void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float 
 }
 
 /* patchgrid.cpp:213-275 + :377-397 (usefbcon = 0) */
-void dis_grid_aggregate(const dis_grid *g, const dis_params *p, float *flowout)
+void dis_grid_aggregate(const dis_grid *g, const dis_params *p, dis_real *flowout)
 {
   dis_grid_aggregate_fb(g, NULL, p, flowout);
 }
 
-void dis_grid_aggregate_fb(const dis_grid *g, const dis_grid *cg, const dis_params *p, float *flowout)
+void dis_grid_aggregate_fb(const dis_grid *g, const dis_grid *cg, const dis_params *p, dis_real *flowout)
 {
   const int ps = g->ps, noc = g->noc, nv = ps * ps * noc, w = g->w, h = g->h;
-  const float minerr = 2.0f;                                         /* oflow.h:62 */
+  const dis_real minerr = 2.0f;                                         /* oflow.h:62 */
   const int np = g->depth ? 1 : 2;                                   /* op->nop (oflow.cpp:76-80) */
-  float *we = (float *)calloc((size_t)w * h, sizeof(float));
-  memset(flowout, 0, sizeof(float) * np * (size_t)w * h);
+  dis_real *we = (dis_real *)calloc((size_t)w * h, sizeof(dis_real));
+  memset(flowout, 0, sizeof(dis_real) * np * (size_t)w * h);
   (void)p;
   for (int ip = 0; ip < g->nop; ++ip) {
-    const float f0 = g->p_iter[2 * ip], f1 = g->p_iter[2 * ip + 1];
-    const float *pw = g->pweight + (size_t)ip * nv;
+    const dis_real f0 = g->p_iter[2 * ip], f1 = g->p_iter[2 * ip + 1];
+    const dis_real *pw = g->pweight + (size_t)ip * nv;
     int lb = -ps / 2, ub = ps / 2 - 1;
     for (int y = lb; y <= ub; ++y) for (int x = lb; x <= ub; ++x, ++pw) {
       int yt = (int)(y + g->pt_ref[2 * ip + 1]);
       int xt = (int)(x + g->pt_ref[2 * ip]);
       if (xt >= 0 && yt >= 0 && xt < w && yt < h) {
         int i = yt * w + xt;
-        float absw;
-        if (noc == 1) absw = 1.0f / (float)(*pw > minerr ? *pw : minerr);
+        dis_real absw;
+        if (noc == 1) absw = 1.0f / (dis_real)(*pw > minerr ? *pw : minerr);
         else {
           /* :253-258: the pointer advances 3 per in-image pixel but only 1 per skipped pixel
              (reference behaviour, kept as is) */
-          absw = (float)(*pw > minerr ? *pw : minerr); ++pw;
-          absw += (float)(*pw > minerr ? *pw : minerr); ++pw;
-          absw += (float)(*pw > minerr ? *pw : minerr);
+          absw = (dis_real)(*pw > minerr ? *pw : minerr); ++pw;
+          absw += (dis_real)(*pw > minerr ? *pw : minerr); ++pw;
+          absw += (dis_real)(*pw > minerr ? *pw : minerr);
           absw = 1.0f / absw;
         }
         we[i] += absw;
@@ -562,26 +580,26 @@ void dis_grid_aggregate_fb(const dis_grid *g, const dis_grid *cg, const dis_para
   /* patchgrid.cpp:278-375: the complementary grid's patches, at their position after optimisation (pt_iter), with
      bilinear weights and reversed flow; same serial order (patch id, window row, window column, taps cc fc cf ff) */
   for (int ip = 0; cg && ip < cg->nop; ++ip) {
-    const float f0 = cg->p_iter[2 * ip], f1 = cg->p_iter[2 * ip + 1];
-    const float *pw = cg->pweight + (size_t)ip * nv;
-    const float rx = cg->pt_ref[2 * ip] + f0, ry = cg->pt_ref[2 * ip + 1] + f1;      /* GetPointPos() = pt_iter (patch.cpp:214-221) */
+    const dis_real f0 = cg->p_iter[2 * ip], f1 = cg->p_iter[2 * ip + 1];
+    const dis_real *pw = cg->pweight + (size_t)ip * nv;
+    const dis_real rx = cg->pt_ref[2 * ip] + f0, ry = cg->pt_ref[2 * ip + 1] + f1;      /* GetPointPos() = pt_iter (patch.cpp:214-221) */
     const int pos0 = (int)ceil(rx + .00001), pos1 = (int)ceil(ry + .00001);        /* :302-305 (double arithmetic) */
-    const int pos2 = (int)floorf(rx), pos3 = (int)floorf(ry);
-    const float r0 = rx - pos2, r1 = ry - pos3;
-    const float wb0 = r0 * r1, wb1 = (1 - r0) * r1, wb2 = r0 * (1 - r1), wb3 = (1 - r0) * (1 - r1);
+    const int pos2 = (int)DIS_FLOOR(rx), pos3 = (int)DIS_FLOOR(ry);
+    const dis_real r0 = rx - pos2, r1 = ry - pos3;
+    const dis_real wb0 = r0 * r1, wb1 = (1 - r0) * r1, wb2 = r0 * (1 - r1), wb3 = (1 - r0) * (1 - r1);
     int lb = -ps / 2, ub = ps / 2 - 1;
     for (int y = lb; y <= ub; ++y) for (int x = lb; x <= ub; ++x, ++pw) {
       int yt = y + pos1, xt = x + pos0;
       if (xt >= 1 && yt >= 1 && xt < (w - 1) && yt < (h - 1)) {
-        float absw;
-        if (noc == 1) absw = 1.0f / (float)(*pw > minerr ? *pw : minerr);
+        dis_real absw;
+        if (noc == 1) absw = 1.0f / (dis_real)(*pw > minerr ? *pw : minerr);
         else {
-          absw = (float)(*pw > minerr ? *pw : minerr); ++pw;
-          absw += (float)(*pw > minerr ? *pw : minerr); ++pw;
-          absw += (float)(*pw > minerr ? *pw : minerr);
+          absw = (dis_real)(*pw > minerr ? *pw : minerr); ++pw;
+          absw += (dis_real)(*pw > minerr ? *pw : minerr); ++pw;
+          absw += (dis_real)(*pw > minerr ? *pw : minerr);
           absw = 1.0f / absw;
         }
-        const float n0 = f0 * absw, n1 = f1 * absw;
+        const dis_real n0 = f0 * absw, n1 = f1 * absw;
         const int cc = xt + yt * w, fc = (xt - 1) + yt * w, cf = xt + (yt - 1) * w, ff = (xt - 1) + (yt - 1) * w;
         we[cc] += wb0 * absw; we[fc] += wb1 * absw; we[cf] += wb2 * absw; we[ff] += wb3 * absw;
         if (np == 1) {                                               /* :365-368 */
@@ -611,19 +629,19 @@ int dis_stride(int w) { return ((w + 3) / 4) * 4; }                  /* image.c:
 static int clampi(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
 /* FDF1.0.1/opticalflow_aux.c:18-60 */
-void dis_image_warp(float *dst, float *mask, const float *src, const float *wx, const float *wy,
+void dis_image_warp(dis_real *dst, dis_real *mask, const dis_real *src, const dis_real *wx, const dis_real *wy,
                     int w, int h, int noc)
 {
   const int st = dis_stride(w);
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
     const int o = j * st + i;
-    float xx = i + wx[o], yy = j + wy[o];
+    dis_real xx = i + wx[o], yy = j + wy[o];
     int x = (int)floor(xx), y = (int)floor(yy);
-    float dx = xx - x, dy = yy - y;
+    dis_real dx = xx - x, dy = yy - y;
     mask[o] = (xx >= 0 && xx <= w - 1 && yy >= 0 && yy <= h - 1);
     int x1 = clampi(x, w), x2 = clampi(x + 1, w), y1 = clampi(y, h), y2 = clampi(y + 1, h);
     for (int c = 0; c < noc; ++c) {
-      const float *s = src + (size_t)c * st * h;
+      const dis_real *s = src + (size_t)c * st * h;
       dst[(size_t)c * st * h + o] =
           s[y1 * st + x1] * (1.0f - dx) * (1.0f - dy) +
           s[y1 * st + x2] * dx * (1.0f - dy) +
@@ -641,21 +659,21 @@ static void deriv5(float c[5])
   c[0] = h2; c[1] = h1; c[2] = -0.0f; c[3] = -h1; c[4] = -h2;
 }
 /* convolve_horiz_fast_5 image.c:466-502 (replicate borders) */
-static void conv_h5(float *dst, const float *src, int w, int h)
+static void conv_h5(dis_real *dst, const dis_real *src, int w, int h)
 {
   const int st = dis_stride(w); float c[5]; deriv5(c);
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
-    const float *r = src + j * st;
+    const dis_real *r = src + j * st;
     dst[j * st + i] = c[0] * r[clampi(i - 2, w)] + c[1] * r[clampi(i - 1, w)] + c[2] * r[i] +
                       c[3] * r[clampi(i + 1, w)] + c[4] * r[clampi(i + 2, w)];
   }
 }
 /* convolve_vert_fast_5 image.c:401-434 (border rows use summed coefficients) */
-static void conv_v5(float *dst, const float *src, int w, int h)
+static void conv_v5(dis_real *dst, const dis_real *src, int w, int h)
 {
   const int st = dis_stride(w); float c[5]; deriv5(c);
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
-    const float *s = src + i; float v;
+    const dis_real *s = src + i; dis_real v;
 #define S(r) s[(r) * st]
     if (j == 0) v = (c[0] + c[1] + c[2]) * S(0) + c[3] * S(1) + c[4] * S(2);
     else if (j == 1) v = (c[0] + c[1]) * S(0) + c[2] * S(1) + c[3] * S(2) + c[4] * S(3);
@@ -667,20 +685,20 @@ static void conv_v5(float *dst, const float *src, int w, int h)
   }
 }
 /* convolution_new(1,{0,-0.5},0) -> {-0.5,-0,0.5}; convolve_horiz_fast_3 image.c:436-464 */
-static void conv_h3(float *dst, const float *src, int w, int h)
+static void conv_h3(dis_real *dst, const dis_real *src, int w, int h)
 {
   const int st = dis_stride(w); const float c0 = -0.5f, c1 = -0.0f, c2 = 0.5f;
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
-    const float *r = src + j * st;
+    const dis_real *r = src + j * st;
     dst[j * st + i] = c0 * r[clampi(i - 1, w)] + c1 * r[i] + c2 * r[clampi(i + 1, w)];
   }
 }
 /* convolve_vert_fast_3 image.c:376-399 */
-static void conv_v3(float *dst, const float *src, int w, int h)
+static void conv_v3(dis_real *dst, const dis_real *src, int w, int h)
 {
   const int st = dis_stride(w); const float c0 = -0.5f, c1 = -0.0f, c2 = 0.5f;
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
-    const float *s = src + i; float v;
+    const dis_real *s = src + i; dis_real v;
     if (j == 0) v = (c0 + c1) * s[0] + c2 * s[st];
     else if (j == h - 1) v = c0 * s[(j - 1) * st] + (c1 + c2) * s[j * st];
     else v = c0 * s[(j - 1) * st] + c1 * s[j * st] + c2 * s[(j + 1) * st];
@@ -689,12 +707,12 @@ static void conv_v3(float *dst, const float *src, int w, int h)
 }
 
 /* FDF1.0.1/opticalflow_aux.c:65-116 */
-void dis_get_derivatives(const float *im1, const float *im2w, int w, int h, int noc,
-                         float *Ix, float *Iy, float *Iz, float *Ixx, float *Ixy, float *Iyy,
-                         float *Ixz, float *Iyz)
+void dis_get_derivatives(const dis_real *im1, const dis_real *im2w, int w, int h, int noc,
+                         dis_real *Ix, dis_real *Iy, dis_real *Iz, dis_real *Ixx, dis_real *Ixy, dis_real *Iyy,
+                         dis_real *Ixz, dis_real *Iyz)
 {
   const int st = dis_stride(w); const size_t pl = (size_t)st * h;
-  float *avg = (float *)calloc(pl * noc, sizeof(float));
+  dis_real *avg = (dis_real *)calloc(pl * noc, sizeof(dis_real));
   for (int c = 0; c < noc; ++c) for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
     size_t o = c * pl + j * st + i;
     avg[o] = 0.5f * (im2w[o] + im1[o]);
@@ -714,16 +732,16 @@ void dis_get_derivatives(const float *im1, const float *im2w, int w, int h, int 
 }
 
 /* FDF1.0.1/opticalflow_aux.c:123-165 */
-void dis_compute_smoothness(float *horiz, float *vert, const float *uu, const float *vv,
-                            int w, int h, float quarter_alpha)
+void dis_compute_smoothness(dis_real *horiz, dis_real *vert, const dis_real *uu, const dis_real *vv,
+                            int w, int h, dis_real quarter_alpha)
 {
   const int st = dis_stride(w); const size_t pl = (size_t)st * h;
   const float eps = 0.001f * 0.001f;
-  float *ux = (float *)calloc(pl * 5, sizeof(float)), *vx = ux + pl, *uy = vx + pl, *vy = uy + pl, *s = vy + pl;
+  dis_real *ux = (dis_real *)calloc(pl * 5, sizeof(dis_real)), *vx = ux + pl, *uy = vx + pl, *vy = uy + pl, *s = vy + pl;
   conv_h3(ux, uu, w, h); conv_h3(vx, vv, w, h); conv_v3(uy, uu, w, h); conv_v3(vy, vv, w, h);
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
     int o = j * st + i;
-    s[o] = quarter_alpha / sqrtf(ux[o] * ux[o] + uy[o] * uy[o] + vx[o] * vx[o] + vy[o] * vy[o] + eps);
+    s[o] = quarter_alpha / DIS_SQRT(ux[o] * ux[o] + uy[o] * uy[o] + vx[o] * vx[o] + vy[o] * vy[o] + eps);
   }
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
     int o = j * st + i;
@@ -734,24 +752,24 @@ void dis_compute_smoothness(float *horiz, float *vert, const float *uu, const fl
 }
 
 /* FDF1.0.1/opticalflow_aux.c:310-438 */
-void dis_compute_data(float *a11, float *a12, float *a22, float *b1, float *b2,
-                      const float *mask, const float *du, const float *dv,
-                      const float *Ix, const float *Iy, const float *Iz, const float *Ixx,
-                      const float *Ixy, const float *Iyy, const float *Ixz, const float *Iyz,
-                      int w, int h, int noc, float half_delta_over3, float half_gamma_over3)
+void dis_compute_data(dis_real *a11, dis_real *a12, dis_real *a22, dis_real *b1, dis_real *b2,
+                      const dis_real *mask, const dis_real *du, const dis_real *dv,
+                      const dis_real *Ix, const dis_real *Iy, const dis_real *Iz, const dis_real *Ixx,
+                      const dis_real *Ixy, const dis_real *Iyy, const dis_real *Ixz, const dis_real *Iyz,
+                      int w, int h, int noc, dis_real half_delta_over3, dis_real half_gamma_over3)
 {
   const int st = dis_stride(w); const size_t pl = (size_t)st * h;
   const float dnorm = 0.1f * 0.1f, epsc = 0.001f * 0.001f, epsg = 0.001f * 0.001f;
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
     const int o = j * st + i;
-    float A11 = 0, A12 = 0, A22 = 0, B1 = 0, B2 = 0;
-    const float u = du[o], v = dv[o], m = mask[o];
+    dis_real A11 = 0, A12 = 0, A22 = 0, B1 = 0, B2 = 0;
+    const dis_real u = du[o], v = dv[o], m = mask[o];
     if (noc == 1) {
-      float tmp, tmp2, n1, n2;
+      dis_real tmp, tmp2, n1, n2;
       if (half_delta_over3) {
         tmp = Iz[o] + Ix[o] * u + Iy[o] * v;
         n1 = Ix[o] * Ix[o] + Iy[o] * Iy[o] + dnorm;
-        tmp = m * half_delta_over3 / sqrtf(3 * tmp * tmp / n1 + epsc);
+        tmp = m * half_delta_over3 / DIS_SQRT(3 * tmp * tmp / n1 + epsc);
         tmp /= n1;
         A11 += tmp * Ix[o] * Ix[o];
         A12 += tmp * Ix[o] * Iy[o];
@@ -763,7 +781,7 @@ void dis_compute_data(float *a11, float *a12, float *a22, float *b1, float *b2,
       n2 = Iyy[o] * Iyy[o] + Ixy[o] * Ixy[o] + dnorm;
       tmp = Ixz[o] + Ixx[o] * u + Ixy[o] * v;
       tmp2 = Iyz[o] + Ixy[o] * u + Iyy[o] * v;
-      tmp = m * half_gamma_over3 / sqrtf(3 * tmp * tmp / n1 + 3 * tmp2 * tmp2 / n2 + epsg);
+      tmp = m * half_gamma_over3 / DIS_SQRT(3 * tmp * tmp / n1 + 3 * tmp2 * tmp2 / n2 + epsg);
       tmp2 = tmp / n2; tmp /= n1;
       A11 += tmp * Ixx[o] * Ixx[o] + tmp2 * Ixy[o] * Ixy[o];
       A12 += tmp * Ixx[o] * Ixy[o] + tmp2 * Ixy[o] * Iyy[o];
@@ -772,17 +790,17 @@ void dis_compute_data(float *a11, float *a12, float *a22, float *b1, float *b2,
       B2 -= tmp2 * Iyy[o] * Iyz[o] + tmp * Ixy[o] * Ixz[o];
       A11 *= 3; A12 *= 3; A22 *= 3; B1 *= 3; B2 *= 3;               /* :420-426 */
     } else {
-      const float *ix1 = Ix, *ix2 = Ix + pl, *ix3 = Ix + 2 * pl, *iy1 = Iy, *iy2 = Iy + pl, *iy3 = Iy + 2 * pl;
-      const float *iz1 = Iz, *iz2 = Iz + pl, *iz3 = Iz + 2 * pl;
-      const float *ixx1 = Ixx, *ixx2 = Ixx + pl, *ixx3 = Ixx + 2 * pl, *ixy1 = Ixy, *ixy2 = Ixy + pl, *ixy3 = Ixy + 2 * pl;
-      const float *iyy1 = Iyy, *iyy2 = Iyy + pl, *iyy3 = Iyy + 2 * pl, *ixz1 = Ixz, *ixz2 = Ixz + pl, *ixz3 = Ixz + 2 * pl;
-      const float *iyz1 = Iyz, *iyz2 = Iyz + pl, *iyz3 = Iyz + 2 * pl;
-      float tmp, tmp2, tmp3, tmp4, tmp5, tmp6, n1, n2, n3, n4, n5, n6;
+      const dis_real *ix1 = Ix, *ix2 = Ix + pl, *ix3 = Ix + 2 * pl, *iy1 = Iy, *iy2 = Iy + pl, *iy3 = Iy + 2 * pl;
+      const dis_real *iz1 = Iz, *iz2 = Iz + pl, *iz3 = Iz + 2 * pl;
+      const dis_real *ixx1 = Ixx, *ixx2 = Ixx + pl, *ixx3 = Ixx + 2 * pl, *ixy1 = Ixy, *ixy2 = Ixy + pl, *ixy3 = Ixy + 2 * pl;
+      const dis_real *iyy1 = Iyy, *iyy2 = Iyy + pl, *iyy3 = Iyy + 2 * pl, *ixz1 = Ixz, *ixz2 = Ixz + pl, *ixz3 = Ixz + 2 * pl;
+      const dis_real *iyz1 = Iyz, *iyz2 = Iyz + pl, *iyz3 = Iyz + 2 * pl;
+      dis_real tmp, tmp2, tmp3, tmp4, tmp5, tmp6, n1, n2, n3, n4, n5, n6;
       if (half_delta_over3) {
         tmp = iz1[o] + ix1[o] * u + iy1[o] * v;  n1 = ix1[o] * ix1[o] + iy1[o] * iy1[o] + dnorm;
         tmp2 = iz2[o] + ix2[o] * u + iy2[o] * v; n2 = ix2[o] * ix2[o] + iy2[o] * iy2[o] + dnorm;
         tmp3 = iz3[o] + ix3[o] * u + iy3[o] * v; n3 = ix3[o] * ix3[o] + iy3[o] * iy3[o] + dnorm;
-        tmp = m * half_delta_over3 / sqrtf(tmp * tmp / n1 + tmp2 * tmp2 / n2 + tmp3 * tmp3 / n3 + epsc);
+        tmp = m * half_delta_over3 / DIS_SQRT(tmp * tmp / n1 + tmp2 * tmp2 / n2 + tmp3 * tmp3 / n3 + epsc);
         tmp3 = tmp / n3; tmp2 = tmp / n2; tmp /= n1;
         A11 += tmp * ix1[o] * ix1[o]; A12 += tmp * ix1[o] * iy1[o]; A22 += tmp * iy1[o] * iy1[o];
         B1 -= tmp * iz1[o] * ix1[o];  B2 -= tmp * iz1[o] * iy1[o];
@@ -797,7 +815,7 @@ void dis_compute_data(float *a11, float *a12, float *a22, float *b1, float *b2,
       tmp3 = ixz2[o] + ixx2[o] * u + ixy2[o] * v;         tmp4 = iyz2[o] + ixy2[o] * u + iyy2[o] * v;
       n5 = ixx3[o] * ixx3[o] + ixy3[o] * ixy3[o] + dnorm; n6 = iyy3[o] * iyy3[o] + ixy3[o] * ixy3[o] + dnorm;
       tmp5 = ixz3[o] + ixx3[o] * u + ixy3[o] * v;         tmp6 = iyz3[o] + ixy3[o] * u + iyy3[o] * v;
-      tmp = m * half_gamma_over3 / sqrtf(tmp * tmp / n1 + tmp2 * tmp2 / n2 + tmp3 * tmp3 / n3 +
+      tmp = m * half_gamma_over3 / DIS_SQRT(tmp * tmp / n1 + tmp2 * tmp2 / n2 + tmp3 * tmp3 / n3 +
                                          tmp4 * tmp4 / n4 + tmp5 * tmp5 / n5 + tmp6 * tmp6 / n6 + epsg);
       tmp6 = tmp / n6; tmp5 = tmp / n5; tmp4 = tmp / n4; tmp3 = tmp / n3; tmp2 = tmp / n2; tmp /= n1;
       A11 += tmp * ixx1[o] * ixx1[o] + tmp2 * ixy1[o] * ixy1[o];
@@ -823,12 +841,12 @@ void dis_compute_data(float *a11, float *a12, float *a22, float *b1, float *b2,
 /* FDF1.0.1/opticalflow_aux.c:172-199.  Scatter form of the reference turned into its per-pixel
  * gather with the same order of the four updates: -left, +right (horizontal pass, :177-190),
  * then -top, +bottom (vertical pass, :192-198). */
-void dis_sub_laplacian(float *dst, const float *src, const float *horiz, const float *vert, int w, int h)
+void dis_sub_laplacian(dis_real *dst, const dis_real *src, const dis_real *horiz, const dis_real *vert, int w, int h)
 {
   const int st = dis_stride(w);
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
     const int o = j * st + i;
-    float v = dst[o];
+    dis_real v = dst[o];
     if (i > 0)     v -= horiz[o - 1] * (src[o] - src[o - 1]);
     if (i < w - 1) v += horiz[o] * (src[o + 1] - src[o]);
     if (j > 0)     v -= vert[o - st] * (src[o] - src[o - st]);
@@ -839,41 +857,41 @@ void dis_sub_laplacian(float *dst, const float *src, const float *horiz, const f
 
 /* FDF1.0.1/solver.c:77-421 sor_coupled: lexicographic Gauss-Seidel with exact 2x2 block inverse.
  * First sweep inverts the blocks in place (:115-120, note a11/a22 swap = adjugate). */
-static void sor_invert_blocks(float *a11, float *a12, float *a22, const float *horiz, const float *vert, int w, int h)
+static void sor_invert_blocks(dis_real *a11, dis_real *a12, dis_real *a22, const dis_real *horiz, const dis_real *vert, int w, int h)
 {
   const int st = dis_stride(w);
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
     const int o = j * st + i;
-    const float hl = i > 0 ? horiz[o - 1] : 0.0f, hr = horiz[o];
-    float dps = hl + hr;                                              /* (*hpl)+(*hp) */
+    const dis_real hl = i > 0 ? horiz[o - 1] : 0.0f, hr = horiz[o];
+    dis_real dps = hl + hr;                                              /* (*hpl)+(*hp) */
     if (j > 0) dps = dps + vert[o - st];                              /* +(*vpt) */
     if (j < h - 1) dps = dps + vert[o];                               /* +(*vp) */
-    const float A11 = a22[o] + dps, A22 = a11[o] + dps;
-    const float det = A11 * A22 - a12[o] * a12[o];
+    const dis_real A11 = a22[o] + dps, A22 = a11[o] + dps;
+    const dis_real det = A11 * A22 - a12[o] * a12[o];
     a11[o] = A11 / det; a22[o] = A22 / det; a12[o] = a12[o] / -det;
   }
 }
 
-static inline void sor_pixel(float *du, float *dv, const float *a11, const float *a12, const float *a22,
-                             const float *b1, const float *b2, const float *horiz, const float *vert,
-                             int i, int j, int w, int h, int st, float omega)
+static inline void sor_pixel(dis_real *du, dis_real *dv, const dis_real *a11, const dis_real *a12, const dis_real *a22,
+                             const dis_real *b1, const dis_real *b2, const dis_real *horiz, const dis_real *vert,
+                             int i, int j, int w, int h, int st, dis_real omega)
 {
   const int o = j * st + i;
-  const float hr = horiz[o];
-  const float dur = (i < w - 1) ? du[o + 1] : 0.0f, dvr = (i < w - 1) ? dv[o + 1] : 0.0f;
-  float s1 = hr * dur, s2 = hr * dvr;                                 /* (*hp)*(*dur) */
+  const dis_real hr = horiz[o];
+  const dis_real dur = (i < w - 1) ? du[o + 1] : 0.0f, dvr = (i < w - 1) ? dv[o + 1] : 0.0f;
+  dis_real s1 = hr * dur, s2 = hr * dvr;                                 /* (*hp)*(*dur) */
   if (j > 0) { s1 = s1 + vert[o - st] * du[o - st]; s2 = s2 + vert[o - st] * dv[o - st]; }
   if (j < h - 1) { s1 = s1 + vert[o] * du[o + st]; s2 = s2 + vert[o] * dv[o + st]; }
   s1 = s1 + b1[o]; s2 = s2 + b2[o];
-  float B1 = s1, B2 = s2;
+  dis_real B1 = s1, B2 = s2;
   if (i > 0) { B1 = horiz[o - 1] * du[o - 1] + s1; B2 = horiz[o - 1] * dv[o - 1] + s2; }
   du[o] += omega * (a11[o] * B1 + a12[o] * B2 - du[o]);
   dv[o] += omega * (a12[o] * B1 + a22[o] * B2 - dv[o]);
 }
 
-void dis_sor_coupled(float *du, float *dv, float *a11, float *a12, float *a22, const float *b1,
-                     const float *b2, const float *horiz, const float *vert, int w, int h,
-                     int iterations, float omega)
+void dis_sor_coupled(dis_real *du, dis_real *dv, dis_real *a11, dis_real *a12, dis_real *a22, const dis_real *b1,
+                     const dis_real *b2, const dis_real *horiz, const dis_real *vert, int w, int h,
+                     int iterations, dis_real omega)
 {
   const int st = dis_stride(w);
   if (iterations < 1) return;
@@ -883,9 +901,9 @@ void dis_sor_coupled(float *du, float *dv, float *a11, float *a12, float *a22, c
       sor_pixel(du, dv, a11, a12, a22, b1, b2, horiz, vert, i, j, w, h, st, omega);
 }
 
-void dis_sor_coupled_redblack(float *du, float *dv, float *a11, float *a12, float *a22,
-                              const float *b1, const float *b2, const float *horiz,
-                              const float *vert, int w, int h, int iterations, float omega)
+void dis_sor_coupled_redblack(dis_real *du, dis_real *dv, dis_real *a11, dis_real *a12, dis_real *a22,
+                              const dis_real *b1, const dis_real *b2, const dis_real *horiz,
+                              const dis_real *vert, int w, int h, int iterations, dis_real omega)
 {
   const int st = dis_stride(w);
   if (iterations < 1) return;
@@ -901,41 +919,41 @@ void dis_sor_coupled_redblack(float *du, float *dv, float *a11, float *a12, floa
  * selects (refine_variational.cpp:202-206).  Point update -- du from the old dv, then dv from the NEW du, no block inverse --
  * in the row-major order of the serial loop (without OpenMP the `parallel for` over rows is a plain loop; with it the rows race,
  * SURVEY 8a probe).  Neighbour order of the sums: top, left, bottom, right.  a11 / a12 / a22 are NOT modified. */
-void dis_sor_coupled_slow(float *du, float *dv, const float *a11, const float *a12, const float *a22, const float *b1,
-                          const float *b2, const float *horiz, const float *vert, int w, int h, int iterations, float omega)
+void dis_sor_coupled_slow(dis_real *du, dis_real *dv, const dis_real *a11, const dis_real *a12, const dis_real *a22, const dis_real *b1,
+                          const dis_real *b2, const dis_real *horiz, const dis_real *vert, int w, int h, int iterations, dis_real omega)
 {
   const int st = dis_stride(w);
   for (int it = 0; it < iterations; ++it)
     for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
       const int o = j * st + i;
-      float sigma_u = 0.0f, sigma_v = 0.0f, sum_dpsis = 0.0f;
+      dis_real sigma_u = 0.0f, sigma_v = 0.0f, sum_dpsis = 0.0f;
       if (j > 0)     { sigma_u -= vert[o - st] * du[o - st]; sigma_v -= vert[o - st] * dv[o - st]; sum_dpsis += vert[o - st]; }
       if (i > 0)     { sigma_u -= horiz[o - 1] * du[o - 1];  sigma_v -= horiz[o - 1] * dv[o - 1];  sum_dpsis += horiz[o - 1]; }
       if (j < h - 1) { sigma_u -= vert[o] * du[o + st];      sigma_v -= vert[o] * dv[o + st];      sum_dpsis += vert[o]; }
       if (i < w - 1) { sigma_u -= horiz[o] * du[o + 1];      sigma_v -= horiz[o] * dv[o + 1];      sum_dpsis += horiz[o]; }
-      const float A11 = a11[o] + sum_dpsis, A12 = a12[o], A22 = a22[o] + sum_dpsis;
-      const float B1 = b1[o] - sigma_u, B2 = b2[o] - sigma_v;
+      const dis_real A11 = a11[o] + sum_dpsis, A12 = a12[o], A22 = a22[o] + sum_dpsis;
+      const dis_real B1 = b1[o] - sigma_u, B2 = b2[o] - sigma_v;
       du[o] = (1.0f - omega) * du[o] + omega / A11 * (B1 - A12 * dv[o]);        /* :63 */
       dv[o] = (1.0f - omega) * dv[o] + omega / A22 * (B2 - A12 * du[o]);        /* :64, with the du just written */
     }
 }
 
 /* kroeger/refine_variational.cpp:25-116 (ctor), :118-149 copyimage, :153-241 RefLevelOF */
-void dis_varref(const float *I0, const float *I1, int w, int h, int lvl, const dis_params *p,
-                float *flow, int sor_mode)
+void dis_varref(const dis_real *I0, const dis_real *I1, int w, int h, int lvl, const dis_params *p,
+                dis_real *flow, int sor_mode)
 {
   const int st = dis_stride(w), noc = p->noc, pad = p->ps, tmp_w = w + 2 * pad;
   const size_t pl = (size_t)st * h;
-  const float quarter_alpha = 0.25f * p->tv_alpha;
-  const float half_gamma_over3 = p->tv_gamma * 0.5f / 3.0f;
-  const float half_delta_over3 = p->tv_delta * 0.5f / 3.0f;
+  const float quarter_alpha = 0.25f * DIS_F32(p->tv_alpha);
+  const float half_gamma_over3 = DIS_F32(p->tv_gamma) * 0.5f / 3.0f;
+  const float half_delta_over3 = DIS_F32(p->tv_delta) * 0.5f / 3.0f;
   const int inner = p->tv_innerit * (lvl + 1);
-  float *buf = (float *)calloc(pl * (13 + 11 * noc), sizeof(float));
-  float *wx = buf, *wy = wx + pl, *du = wy + pl, *dv = du + pl, *mask = dv + pl, *sh = mask + pl,
+  dis_real *buf = (dis_real *)calloc(pl * (13 + 11 * noc), sizeof(dis_real));
+  dis_real *wx = buf, *wy = wx + pl, *du = wy + pl, *dv = du + pl, *mask = dv + pl, *sh = mask + pl,
         *sv = sh + pl, *uu = sv + pl, *vv = uu + pl, *a11 = vv + pl, *a12 = a11 + pl, *a22 = a12 + pl,
         *b1 = a22 + pl;
-  float *b2 = (float *)calloc(pl, sizeof(float));
-  float *im1 = b1 + pl, *im2 = im1 + pl * noc, *w2 = im2 + pl * noc, *Ix = w2 + pl * noc,
+  dis_real *b2 = (dis_real *)calloc(pl, sizeof(dis_real));
+  dis_real *im1 = b1 + pl, *im2 = im1 + pl * noc, *w2 = im2 + pl * noc, *Ix = w2 + pl * noc,
         *Iy = Ix + pl * noc, *Iz = Iy + pl * noc, *Ixx = Iz + pl * noc, *Ixy = Ixx + pl * noc,
         *Iyy = Ixy + pl * noc, *Ixz = Iyy + pl * noc, *Iyz = Ixz + pl * noc;
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
@@ -947,7 +965,7 @@ void dis_varref(const float *I0, const float *I1, int w, int h, int lvl, const d
   }
   dis_image_warp(w2, mask, im2, wx, wy, w, h, noc);
   dis_get_derivatives(im1, w2, w, h, noc, Ix, Iy, Iz, Ixx, Ixy, Iyy, Ixz, Iyz);
-  memcpy(uu, wx, pl * sizeof(float)); memcpy(vv, wy, pl * sizeof(float));
+  memcpy(uu, wx, pl * sizeof(dis_real)); memcpy(vv, wy, pl * sizeof(dis_real));
   for (int it = 0; it < inner; ++it) {
     dis_compute_smoothness(sh, sv, uu, vv, w, h, quarter_alpha);
     dis_compute_data(a11, a12, a22, b1, b2, mask, du, dv, Ix, Iy, Iz, Ixx, Ixy, Iyy, Ixz, Iyz, w, h, noc,
@@ -973,23 +991,23 @@ void dis_varref(const float *I0, const float *I1, int w, int h, int lvl, const d
 /* ------------------------------------------------------------------------------------------- */
 
 /* FDF1.0.1/opticalflow_aux.c:446-540 compute_data_DE: only the horizontal increment du enters */
-void dis_compute_data_de(float *a11, float *b1, const float *mask, const float *du,
-                         const float *Ix, const float *Iy, const float *Iz, const float *Ixx,
-                         const float *Ixy, const float *Iyy, const float *Ixz, const float *Iyz,
-                         int w, int h, int noc, float half_delta_over3, float half_gamma_over3)
+void dis_compute_data_de(dis_real *a11, dis_real *b1, const dis_real *mask, const dis_real *du,
+                         const dis_real *Ix, const dis_real *Iy, const dis_real *Iz, const dis_real *Ixx,
+                         const dis_real *Ixy, const dis_real *Iyy, const dis_real *Ixz, const dis_real *Iyz,
+                         int w, int h, int noc, dis_real half_delta_over3, dis_real half_gamma_over3)
 {
   const int st = dis_stride(w); const size_t pl = (size_t)st * h;
   const float dnorm = 0.1f * 0.1f, epsc = 0.001f * 0.001f, epsg = 0.001f * 0.001f;
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
     const int o = j * st + i;
-    float A11 = 0, B1 = 0;
-    const float u = du[o], m = mask[o];
+    dis_real A11 = 0, B1 = 0;
+    const dis_real u = du[o], m = mask[o];
     if (noc == 1) {
-      float tmp, tmp2, n1, n2;
+      dis_real tmp, tmp2, n1, n2;
       if (half_delta_over3) {                                          /* :481-506 */
         tmp = Iz[o] + Ix[o] * u;
         n1 = Ix[o] * Ix[o] + Iy[o] * Iy[o] + dnorm;
-        tmp = m * half_delta_over3 / sqrtf(3 * tmp * tmp / n1 + epsc);
+        tmp = m * half_delta_over3 / DIS_SQRT(3 * tmp * tmp / n1 + epsc);
         tmp /= n1;
         A11 += tmp * Ix[o] * Ix[o];
         B1 -= tmp * Iz[o] * Ix[o];
@@ -998,39 +1016,39 @@ void dis_compute_data_de(float *a11, float *b1, const float *mask, const float *
       n2 = Iyy[o] * Iyy[o] + Ixy[o] * Ixy[o] + dnorm;
       tmp = Ixz[o] + Ixx[o] * u;
       tmp2 = Iyz[o] + Ixy[o] * u;
-      tmp = m * half_gamma_over3 / sqrtf(3 * tmp * tmp / n1 + 3 * tmp2 * tmp2 / n2 + epsg);   /* :524 */
+      tmp = m * half_gamma_over3 / DIS_SQRT(3 * tmp * tmp / n1 + 3 * tmp2 * tmp2 / n2 + epsg);   /* :524 */
       tmp2 = tmp / n2; tmp /= n1;
       A11 += tmp * Ixx[o] * Ixx[o] + tmp2 * Ixy[o] * Ixy[o];           /* :527-528 */
       B1 -= tmp * Ixx[o] * Ixz[o] + tmp2 * Ixy[o] * Iyz[o];
       A11 *= 3; B1 *= 3;                                               /* :537-540 */
     } else {
-      float t[3], n[3];
+      dis_real t[3], n[3];
       if (half_delta_over3) {
         for (int c = 0; c < 3; ++c) {
           const size_t q = c * pl + o;
           t[c] = Iz[q] + Ix[q] * u;
           n[c] = Ix[q] * Ix[q] + Iy[q] * Iy[q] + dnorm;
         }
-        float tmp = m * half_delta_over3 / sqrtf(t[0] * t[0] / n[0] + t[1] * t[1] / n[1] + t[2] * t[2] / n[2] + epsc);   /* :493 */
-        const float k3 = tmp / n[2], k2 = tmp / n[1]; tmp /= n[0];
-        const float k[3] = {tmp, k2, k3};
+        dis_real tmp = m * half_delta_over3 / DIS_SQRT(t[0] * t[0] / n[0] + t[1] * t[1] / n[1] + t[2] * t[2] / n[2] + epsc);   /* :493 */
+        const dis_real k3 = tmp / n[2], k2 = tmp / n[1]; tmp /= n[0];
+        const dis_real k[3] = {tmp, k2, k3};
         for (int c = 0; c < 3; ++c) {                                  /* :499-506: a11 += ..; b1 -= ..; channel by channel */
           const size_t q = c * pl + o;
           A11 += k[c] * Ix[q] * Ix[q];
           B1 -= k[c] * Iz[q] * Ix[q];
         }
       }
-      float n1[3], n2[3], t1[3], t2[3];
+      dis_real n1[3], n2[3], t1[3], t2[3];
       for (int c = 0; c < 3; ++c) {
         const size_t q = c * pl + o;
         n1[c] = Ixx[q] * Ixx[q] + Ixy[q] * Ixy[q] + dnorm; n2[c] = Iyy[q] * Iyy[q] + Ixy[q] * Ixy[q] + dnorm;
         t1[c] = Ixz[q] + Ixx[q] * u;                       t2[c] = Iyz[q] + Ixy[q] * u;
       }
-      const float tmp = m * half_gamma_over3 / sqrtf(t1[0] * t1[0] / n1[0] + t2[0] * t2[0] / n2[0] + t1[1] * t1[1] / n1[1] +
+      const dis_real tmp = m * half_gamma_over3 / DIS_SQRT(t1[0] * t1[0] / n1[0] + t2[0] * t2[0] / n2[0] + t1[1] * t1[1] / n1[1] +
                                                      t2[1] * t2[1] / n2[1] + t1[2] * t1[2] / n1[2] + t2[2] * t2[2] / n2[2] + epsg);   /* :521 */
       for (int c = 0; c < 3; ++c) {                                    /* :527-535 */
         const size_t q = c * pl + o;
-        const float ka = tmp / n1[c], kb = tmp / n2[c];
+        const dis_real ka = tmp / n1[c], kb = tmp / n2[c];
         A11 += ka * Ixx[q] * Ixx[q] + kb * Ixy[q] * Ixy[q];
         B1 -= ka * Ixx[q] * Ixz[q] + kb * Ixy[q] * Iyz[q];
       }
@@ -1041,38 +1059,38 @@ void dis_compute_data_de(float *a11, float *b1, const float *mask, const float *
 
 /* FDF1.0.1/solver.c:428-466 sor_coupled_slow_but_readable_DE; the default build has no OpenMP, so the row loop is serial:
  * lexicographic Gauss-Seidel.  Neighbour order of the sums: top, left, bottom, right. */
-void dis_sor_de(float *du, const float *a11, const float *b1, const float *horiz, const float *vert,
-                int w, int h, int iterations, float omega)
+void dis_sor_de(dis_real *du, const dis_real *a11, const dis_real *b1, const dis_real *horiz, const dis_real *vert,
+                int w, int h, int iterations, dis_real omega)
 {
   const int st = dis_stride(w);
   for (int it = 0; it < iterations; ++it)
     for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
       const int o = j * st + i;
-      float sigma_u = 0.0f, sum_dpsis = 0.0f;
+      dis_real sigma_u = 0.0f, sum_dpsis = 0.0f;
       if (j > 0)     { sigma_u -= vert[o - st] * du[o - st]; sum_dpsis += vert[o - st]; }
       if (i > 0)     { sigma_u -= horiz[o - 1] * du[o - 1];  sum_dpsis += horiz[o - 1]; }
       if (j < h - 1) { sigma_u -= vert[o] * du[o + st];      sum_dpsis += vert[o]; }
       if (i < w - 1) { sigma_u -= horiz[o] * du[o + 1];      sum_dpsis += horiz[o]; }
-      const float A11 = a11[o] + sum_dpsis;
-      const float B1 = b1[o] - sigma_u;
+      const dis_real A11 = a11[o] + sum_dpsis;
+      const dis_real B1 = b1[o] - sigma_u;
       du[o] = (1.0f - omega) * du[o] + omega * (B1 / A11);
     }
 }
 
 /* kroeger/refine_variational.cpp:25-116 (ctor with noparam = 1), :243-330 RefLevelDE */
-void dis_varref_depth(const float *I0, const float *I1, int w, int h, int lvl, const dis_params *p,
-                      float *flow, int camlr)
+void dis_varref_depth(const dis_real *I0, const dis_real *I1, int w, int h, int lvl, const dis_params *p,
+                      dis_real *flow, int camlr)
 {
   const int st = dis_stride(w), noc = p->noc, pad = p->ps, tmp_w = w + 2 * pad;
   const size_t pl = (size_t)st * h;
-  const float quarter_alpha = 0.25f * p->tv_alpha;
-  const float half_gamma_over3 = p->tv_gamma * 0.5f / 3.0f;
-  const float half_delta_over3 = p->tv_delta * 0.5f / 3.0f;
+  const float quarter_alpha = 0.25f * DIS_F32(p->tv_alpha);
+  const float half_gamma_over3 = DIS_F32(p->tv_gamma) * 0.5f / 3.0f;
+  const float half_delta_over3 = DIS_F32(p->tv_delta) * 0.5f / 3.0f;
   const int inner = p->tv_innerit * (lvl + 1);
-  float *buf = (float *)calloc(pl * (9 + 11 * noc), sizeof(float));
-  float *wx = buf, *wy0 = wx + pl, *du = wy0 + pl, *mask = du + pl, *sh = mask + pl, *sv = sh + pl, *uu = sv + pl,
+  dis_real *buf = (dis_real *)calloc(pl * (9 + 11 * noc), sizeof(dis_real));
+  dis_real *wx = buf, *wy0 = wx + pl, *du = wy0 + pl, *mask = du + pl, *sh = mask + pl, *sv = sh + pl, *uu = sv + pl,
         *a11 = uu + pl, *b1 = a11 + pl;
-  float *im1 = b1 + pl, *im2 = im1 + pl * noc, *w2 = im2 + pl * noc, *Ix = w2 + pl * noc,
+  dis_real *im1 = b1 + pl, *im2 = im1 + pl * noc, *w2 = im2 + pl * noc, *Ix = w2 + pl * noc,
         *Iy = Ix + pl * noc, *Iz = Iy + pl * noc, *Ixx = Iz + pl * noc, *Ixy = Ixx + pl * noc,
         *Iyy = Ixy + pl * noc, *Ixz = Iyy + pl * noc, *Iyz = Ixz + pl * noc;
   for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
@@ -1084,7 +1102,7 @@ void dis_varref_depth(const float *I0, const float *I1, int w, int h, int lvl, c
   }
   dis_image_warp(w2, mask, im2, wx, wy0, w, h, noc);                  /* :273, wy_dummy = 0 */
   dis_get_derivatives(im1, w2, w, h, noc, Ix, Iy, Iz, Ixx, Ixy, Iyy, Ixz, Iyz);
-  memcpy(uu, wx, pl * sizeof(float));
+  memcpy(uu, wx, pl * sizeof(dis_real));
   for (int it = 0; it < inner; ++it) {
     dis_compute_smoothness(sh, sv, uu, wy0, w, h, quarter_alpha);     /* :288 */
     dis_compute_data_de(a11, b1, mask, du, Ix, Iy, Iz, Ixx, Ixy, Iyy, Ixz, Iyz, w, h, noc, half_delta_over3, half_gamma_over3);
@@ -1092,7 +1110,7 @@ void dis_varref_depth(const float *I0, const float *I1, int w, int h, int lvl, c
     dis_sor_de(du, a11, b1, sh, sv, w, h, p->tv_solverit, p->tv_sor);
     for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {         /* :299-314 minps / maxps with zero */
       const int o = j * st + i;
-      const float s = wx[o] + du[o];
+      const dis_real s = wx[o] + du[o];
       uu[o] = camlr == 0 ? (s < 0.0f ? s : 0.0f) : (s > 0.0f ? s : 0.0f);
     }
   }
@@ -1105,26 +1123,26 @@ void dis_varref_depth(const float *I0, const float *I1, int w, int h, int lvl, c
 /* ------------------------------------------------------------------------------------------- */
 
 void dis_flow_pyr(const dis_pyramid *P0, const dis_pyramid *P1, const dis_params *p,
-                  const float *initflow, float *outflow, int sor_mode, float *level_dump)
+                  const dis_real *initflow, dis_real *outflow, int sor_mode, dis_real *level_dump)
 {
   const int ns = p->sc_f - p->sc_l + 1, fb = p->usefbcon != 0, np = p->depth ? 1 : 2;
-  float **flow = (float **)calloc(ns, sizeof(float *)), **flow_bw = (float **)calloc(ns, sizeof(float *));
+  dis_real **flow = (dis_real **)calloc(ns, sizeof(dis_real *)), **flow_bw = (dis_real **)calloc(ns, sizeof(dis_real *));
   size_t dump_off = 0;
   for (int sl = p->sc_f; sl >= p->sc_l; --sl) {
     const int ii = sl - p->sc_l, w = dis_level_w(P0, sl), h = dis_level_h(P0, sl);
     dis_grid *g = dis_grid_new(w, h, sl, p), *gb = fb ? dis_grid_new(w, h, sl, p) : NULL;   /* oflow.cpp:160-170 */
-    flow[ii] = (float *)malloc(sizeof(float) * np * (size_t)w * h);
+    flow[ii] = (dis_real *)malloc(sizeof(dis_real) * np * (size_t)w * h);
     if (gb) gb->camlr = 1;                                            /* oflow.cpp:157,165 */
     dis_grid_init(g, p, P0->im[sl], P0->dx[sl], P0->dy[sl]);
-    if (fb) { flow_bw[ii] = (float *)malloc(sizeof(float) * np * (size_t)w * h); dis_grid_init(gb, p, P1->im[sl], P1->dx[sl], P1->dy[sl]); }   /* :193-197 */
+    if (fb) { flow_bw[ii] = (dis_real *)malloc(sizeof(dis_real) * np * (size_t)w * h); dis_grid_init(gb, p, P1->im[sl], P1->dx[sl], P1->dy[sl]); }   /* :193-197 */
     if (sl < p->sc_f) { dis_grid_init_from_coarser(g, flow[ii + 1]); if (fb) dis_grid_init_from_coarser(gb, flow_bw[ii + 1]); }   /* :209-216 */
     else if (initflow) dis_grid_init_from_coarser(g, initflow);
     dis_grid_optimize(g, p, P1->im[sl], NULL);
     if (fb) dis_grid_optimize(gb, p, P0->im[sl], NULL);                                   /* :233-235 */
-    float *out = (sl == p->sc_l) ? outflow : flow[ii];
+    dis_real *out = (sl == p->sc_l) ? outflow : flow[ii];
     dis_grid_aggregate_fb(g, gb, p, out);
     if (fb && sl > p->sc_l) dis_grid_aggregate_fb(gb, g, p, flow_bw[ii]);                 /* :269-270 */
-    if (level_dump) { memcpy(level_dump + dump_off, out, sizeof(float) * np * (size_t)w * h); dump_off += np * (size_t)w * h; }
+    if (level_dump) { memcpy(level_dump + dump_off, out, sizeof(dis_real) * np * (size_t)w * h); dump_off += np * (size_t)w * h; }
     if (p->usetvref && p->depth) {                                    /* :287-294 with RefLevelDE */
       dis_varref_depth(P0->im[sl], P1->im[sl], w, h, sl, p, out, 0);
       if (fb && sl > p->sc_l) dis_varref_depth(P1->im[sl], P0->im[sl], w, h, sl, p, flow_bw[ii], 1);
@@ -1132,7 +1150,7 @@ void dis_flow_pyr(const dis_pyramid *P0, const dis_pyramid *P1, const dis_params
       dis_varref(P0->im[sl], P1->im[sl], w, h, sl, p, out, sor_mode);
       if (fb && sl > p->sc_l) dis_varref(P1->im[sl], P0->im[sl], w, h, sl, p, flow_bw[ii], sor_mode);   /* :291-294 */
     }
-    if (level_dump) { memcpy(level_dump + dump_off, out, sizeof(float) * np * (size_t)w * h); dump_off += np * (size_t)w * h; }
+    if (level_dump) { memcpy(level_dump + dump_off, out, sizeof(dis_real) * np * (size_t)w * h); dump_off += np * (size_t)w * h; }
     dis_grid_free(g);
     if (gb) dis_grid_free(gb);
   }
@@ -1140,7 +1158,7 @@ void dis_flow_pyr(const dis_pyramid *P0, const dis_pyramid *P1, const dis_params
   free(flow); free(flow_bw);
 }
 
-void dis_flow(const float *I0, const float *I1, int wp, int hp, const dis_params *p, float *outflow, int sor_mode)
+void dis_flow(const dis_real *I0, const dis_real *I1, int wp, int hp, const dis_params *p, dis_real *outflow, int sor_mode)
 {
   dis_pyramid *P0 = dis_pyramid_build(I0, wp, hp, p->noc, p->sc_f, p->ps);
   dis_pyramid *P1 = dis_pyramid_build(I1, wp, hp, p->noc, p->sc_f, p->ps);
@@ -1160,11 +1178,11 @@ void dis_flow(const float *I0, const float *I1, int wp, int hp, const dis_params
 /* out (optional): flows of the first min(n_total, nsrc) pairs.  Returns the timed seconds.       */
 /* ------------------------------------------------------------------------------------------- */
 typedef struct {
-  const float *I0, *I1; long pair_stride; int nsrc, w, h, wp, hp; const dis_params *p; int n_total, with_pyramid;
-  float *out; long out_stride; long next; pthread_barrier_t bar; pthread_mutex_t mu; struct timespec t0, t1; int tid_seq;
+  const dis_real *I0, *I1; long pair_stride; int nsrc, w, h, wp, hp; const dis_params *p; int n_total, with_pyramid;
+  dis_real *out; long out_stride; long next; pthread_barrier_t bar; pthread_mutex_t mu; struct timespec t0, t1; int tid_seq;
 } dis_many;
 
-static void dis_many_pair(dis_many *m, int k, int tid, int first, float *pad0, float *pad1, float *flow, const dis_pyramid *P0, const dis_pyramid *P1)
+static void dis_many_pair(dis_many *m, int k, int tid, int first, dis_real *pad0, dis_real *pad1, dis_real *flow, const dis_pyramid *P0, const dis_pyramid *P1)
 {
   const dis_params *p = m->p;
   /* source pair: k % nsrc with the pyramid in the loop; without it every thread keeps the pyramids of pair tid % nsrc */
@@ -1179,7 +1197,7 @@ static void dis_many_pair(dis_many *m, int k, int tid, int first, float *pad0, f
   /* every output slot is written exactly once, by one thread: with the pyramid in the loop by pair k < nsrc (= its first
    * occurrence), without it by thread tid < nsrc on its first timed pair (`first`) */
   const int store = m->with_pyramid ? (k >= 0 && k < m->nsrc) : (k >= 0 && tid < m->nsrc && first);
-  if (m->out && store && src < m->n_total) memcpy(m->out + (size_t)src * m->out_stride, flow, sizeof(float) * (size_t)m->out_stride);
+  if (m->out && store && src < m->n_total) memcpy(m->out + (size_t)src * m->out_stride, flow, sizeof(dis_real) * (size_t)m->out_stride);
 }
 
 static void *dis_many_worker(void *arg)
@@ -1189,9 +1207,9 @@ static void *dis_many_worker(void *arg)
   tl_pool = &pool;
   const dis_params *p = m->p;
   pthread_mutex_lock(&m->mu); const int tid = m->tid_seq++; pthread_mutex_unlock(&m->mu);
-  float *pad0 = (float *)malloc(sizeof(float) * (size_t)m->wp * m->hp * p->noc);
-  float *pad1 = (float *)malloc(sizeof(float) * (size_t)m->wp * m->hp * p->noc);
-  float *flow = (float *)malloc(sizeof(float) * (size_t)m->out_stride);
+  dis_real *pad0 = (dis_real *)malloc(sizeof(dis_real) * (size_t)m->wp * m->hp * p->noc);
+  dis_real *pad1 = (dis_real *)malloc(sizeof(dis_real) * (size_t)m->wp * m->hp * p->noc);
+  dis_real *flow = (dis_real *)malloc(sizeof(dis_real) * (size_t)m->out_stride);
   dis_pyramid *P0 = NULL, *P1 = NULL;
   if (!m->with_pyramid) {
     const int src = tid % m->nsrc;
@@ -1218,8 +1236,8 @@ static void *dis_many_worker(void *arg)
   return NULL;
 }
 
-double dis_flow_many(const float *I0, const float *I1, long pair_stride, int nsrc, int w, int h, const dis_params *p,
-                     int n_total, int nthreads, int with_pyramid, float *out)
+double dis_flow_many(const dis_real *I0, const dis_real *I1, long pair_stride, int nsrc, int w, int h, const dis_params *p,
+                     int n_total, int nthreads, int with_pyramid, dis_real *out)
 {
   if (nsrc < 1 || nthreads < 1 || n_total < 0) return -1.0;
   dis_many m; memset(&m, 0, sizeof(m));
@@ -1256,40 +1274,40 @@ double dis_flow_many(const float *I0, const float *I1, long pair_stride, int nsr
 
 /* kroeger/run_dense.cpp:407-414.  cv::resize(INTER_LINEAR) upscaling: source coordinate
  * (d+0.5)/s-0.5, clamped (fx=0 at the borders), horizontal pass then vertical pass. */
-void dis_upsample_crop(const float *flow, int wl, int hl, int sc_l, int padw, int padh,
-                       int w_org, int h_org, float *out)
+void dis_upsample_crop(const dis_real *flow, int wl, int hl, int sc_l, int padw, int padh,
+                       int w_org, int h_org, dis_real *out)
 {
   dis_upsample_crop_n(flow, wl, hl, sc_l, padw, padh, w_org, h_org, 2, out);
 }
 
-void dis_upsample_crop_n(const float *flow, int wl, int hl, int sc_l, int padw, int padh,
-                         int w_org, int h_org, int nch, float *out)
+void dis_upsample_crop_n(const dis_real *flow, int wl, int hl, int sc_l, int padw, int padh,
+                         int w_org, int h_org, int nch, dis_real *out)
 {
   const int s = 1 << sc_l, W = wl * s;
   const int x0 = padw / 2, y0 = padh / 2;
-  const float scf = (float)s;
+  const dis_real scf = (dis_real)s;
   const double scale = 1.0 / (double)s;
   for (int y = 0; y < h_org; ++y) {
     int dy = y + y0;
-    float fy = (float)((dy + 0.5) * scale - 0.5);
+    dis_real fy = (dis_real)((dy + 0.5) * scale - 0.5);
     int sy = (int)floor(fy); fy -= sy;
     if (sy < 0) { fy = 0; sy = 0; }
     if (sy >= hl - 1) { fy = 0; sy = hl - 1; }
     int sy1 = sy + 1 < hl ? sy + 1 : hl - 1;
     for (int x = 0; x < w_org; ++x) {
       int dx = x + x0;
-      float fx = (float)((dx + 0.5) * scale - 0.5);
+      dis_real fx = (dis_real)((dx + 0.5) * scale - 0.5);
       int sx = (int)floor(fx); fx -= sx;
       if (sx < 0) { fx = 0; sx = 0; }
       if (sx >= wl - 1) { fx = 0; sx = wl - 1; }
       int sx1 = sx + 1 < wl ? sx + 1 : wl - 1;
       (void)W;
       for (int c = 0; c < nch; ++c) {
-        float v00 = flow[nch * (sy * wl + sx) + c], v01 = flow[nch * (sy * wl + sx1) + c];
-        float v10 = flow[nch * (sy1 * wl + sx) + c], v11 = flow[nch * (sy1 * wl + sx1) + c];
+        dis_real v00 = flow[nch * (sy * wl + sx) + c], v01 = flow[nch * (sy * wl + sx1) + c];
+        dis_real v10 = flow[nch * (sy1 * wl + sx) + c], v11 = flow[nch * (sy1 * wl + sx1) + c];
         if (sc_l != 0) { v00 *= scf; v01 *= scf; v10 *= scf; v11 *= scf; }
-        float r0 = v00 * (1.f - fx) + v01 * fx;
-        float r1 = v10 * (1.f - fx) + v11 * fx;
+        dis_real r0 = v00 * (1.f - fx) + v01 * fx;
+        dis_real r1 = v10 * (1.f - fx) + v11 * fx;
         out[nch * ((size_t)y * w_org + x) + c] = r0 * (1.f - fy) + r1 * fy;
       }
     }

@@ -26,6 +26,18 @@
 extern "C" {
 #endif
 
+/* The real type of every array, parameter and intermediate.  float (the default build, libdis_oracle.so) is the reference's
+ * arithmetic and the one every parity test is pinned to.  -DDIS_REAL_DOUBLE (libdis_oracle_f64.so) compiles the SAME source in
+ * double: the yardstick the tolerance mode is measured against (tests/fast_ref.py).  It solves the same problem: literal
+ * constants keep their f32 values (the `f` suffixes stay) and derived parameters (quarter_alpha, the squared thresholds, the grid
+ * step, the filters' summed border coefficients) are computed in f32 and widened, and the patch sampler's corner rule
+ * ceil(x + 1e-5), an integer decision that f32 takes differently from 256 on, is evaluated on the f32 position in both builds. */
+#ifdef DIS_REAL_DOUBLE
+typedef double dis_real;
+#else
+typedef float dis_real;
+#endif
+
 /* optparam of kroeger/oflow.h:33-76, explicitly set part, plus noc (SELECTCHANNEL 1 -> 1, 3 -> 3) */
 typedef struct dis_params {
   int sc_f;          /* first (coarsest) scale */
@@ -33,18 +45,18 @@ typedef struct dis_params {
   int ps;            /* p_samp_s, patch edge length */
   int max_iter;
   int min_iter;
-  float dp_thresh;   /* NOT squared; squared internally like oflow.cpp:88 */
-  float dr_thresh;
-  float res_thresh;
-  float patove;      /* patch overlap 0..1 */
+  dis_real dp_thresh;   /* NOT squared; squared internally like oflow.cpp:88 */
+  dis_real dr_thresh;
+  dis_real res_thresh;
+  dis_real patove;      /* patch overlap 0..1 */
   int patnorm;
   int noc;           /* 1 gray, 3 RGB */
   int usetvref;
-  float tv_alpha, tv_gamma, tv_delta;
+  dis_real tv_alpha, tv_gamma, tv_delta;
   int tv_innerit, tv_solverit;
-  float tv_sor;
+  dis_real tv_sor;
   int costfct;       /* oflow.h:45: 0 L2, 1 L1, 2 pseudo-Huber (patch.cpp:230-261); the operating points use 0 */
-  float normoutlier; /* oflow.h:63: 5.0, Huber threshold b */
+  dis_real normoutlier; /* oflow.h:63: 5.0, Huber threshold b */
   int usefbcon;      /* oflow.h:44: merge forward and backward flow (patchgrid.cpp:278-375); the operating points use 0 */
   int depth;         /* 0: optical flow (SELECTMODE 1); 1: stereo depth (SELECTMODE 2): one horizontal displacement per
                         pixel/patch (oflow.cpp:76-80 nop = 1), flow arrays have ONE channel */
@@ -55,20 +67,20 @@ int dis_auto_first_scale(int imgwidth, int fratio, int patchsize);
 void dis_op_point(int op, int width_org, int noc, dis_params *p);
 
 /* kroeger/run_dense.cpp:298-311: replicate-pad so W,H are multiples of 2^sc_f.
- * Returns padded sizes; out must hold Wp*Hp*noc floats.  padw/padh returned. */
+ * Returns padded sizes; out must hold Wp*Hp*noc reals.  padw/padh returned. */
 void dis_padded_size(int w, int h, int sc_f, int *wp, int *hp, int *padw, int *padh);
-void dis_pad_frame(const float *in, int w, int h, int noc, int sc_f, float *out);
+void dis_pad_frame(const dis_real *in, int w, int h, int noc, int sc_f, dis_real *out);
 /* kroeger/run_dense.cpp:138-147 (SELECTCHANNEL==2): gradient magnitude of a (padded) frame as the pyramid's input */
-void dis_gradient_magnitude(const float *in, int w, int h, int noc, float *out);
+void dis_gradient_magnitude(const dis_real *in, int w, int h, int noc, dis_real *out);
 
 /* kroeger/run_dense.cpp:130-178.  img: Wp x Hp x noc interleaved f32.  For every level l in
  * 0..sc_f allocates (malloc) padded image / dx / dy of size (w_l+2ps) x (h_l+2ps) x noc.
  * Free with dis_pyramid_free. */
 typedef struct dis_pyramid {
   int nlev, noc, ps, w0, h0;
-  float **im, **dx, **dy;
+  dis_real **im, **dx, **dy;
 } dis_pyramid;
-dis_pyramid *dis_pyramid_build(const float *img, int wp, int hp, int noc, int sc_f, int ps);
+dis_pyramid *dis_pyramid_build(const dis_real *img, int wp, int hp, int noc, int sc_f, int ps);
 void dis_pyramid_free(dis_pyramid *p);
 int dis_level_w(const dis_pyramid *p, int l);
 int dis_level_h(const dis_pyramid *p, int l);
@@ -77,18 +89,18 @@ int dis_level_h(const dis_pyramid *p, int l);
  * L1 residual).  Element e of n belongs to pixel e/noc; pixel q to lane q%64.  Each lane adds its
  * elements in increasing e; the 64 lane sums are then combined by the balanced tree
  * v[i] += v[i^32], ^16, ^8, ^4, ^2, ^1.  (kroeger: Eigen .sum(), patch.cpp:74-76,178-179,278,331.) */
-float dis_sum(const float *v, int n, int noc);
+dis_real dis_sum(const dis_real *v, int n, int noc);
 
 /* ---- patch grid (kroeger/patchgrid.cpp) ---- */
 typedef struct dis_grid {
   int w, h, ps, noc, steps, nopw, noph, nop, pad, tmp_w, lvl;
-  float lb, ubw, ubh;
-  float *pt_ref;   /* nop x 2 */
-  float *p_init;   /* nop x 2 */
-  float *tmpl, *tdx, *tdy;   /* nop x novals */
-  float *hes;      /* nop x 3: H00,H01,H11 */
-  float *p_iter;   /* nop x 2 : result */
-  float *pweight;  /* nop x novals */
+  dis_real lb, ubw, ubh;
+  dis_real *pt_ref;   /* nop x 2 */
+  dis_real *p_init;   /* nop x 2 */
+  dis_real *tmpl, *tdx, *tdy;   /* nop x novals */
+  dis_real *hes;      /* nop x 3: H00,H01,H11 */
+  dis_real *p_iter;   /* nop x 2 : result */
+  dis_real *pweight;  /* nop x novals */
   int   *cnt;      /* nop : iterations run */
   int depth;       /* copy of dis_params.depth */
   int camlr;       /* oflow.h:28, oflow.cpp:153,157: 0 for the forward grid (displacement <= 0), 1 for the backward grid (>= 0);
@@ -96,80 +108,80 @@ typedef struct dis_grid {
 } dis_grid;
 dis_grid *dis_grid_new(int w, int h, int lvl, const dis_params *p);
 void dis_grid_free(dis_grid *g);
-void dis_grid_init(dis_grid *g, const dis_params *p, const float *I0, const float *I0x, const float *I0y);
-void dis_grid_init_from_coarser(dis_grid *g, const float *flow_prev);
-/* trace (optional): per patch (max_iter+1) x 4 floats [p0,p1,mares,cnt] rows; may be NULL */
-void dis_grid_optimize(dis_grid *g, const dis_params *p, const float *I1, float *trace);
-void dis_grid_aggregate(const dis_grid *g, const dis_params *p, float *flowout);
+void dis_grid_init(dis_grid *g, const dis_params *p, const dis_real *I0, const dis_real *I0x, const dis_real *I0y);
+void dis_grid_init_from_coarser(dis_grid *g, const dis_real *flow_prev);
+/* trace (optional): per patch (max_iter+1) x 4 reals [p0,p1,mares,cnt] rows; may be NULL */
+void dis_grid_optimize(dis_grid *g, const dis_params *p, const dis_real *I1, dis_real *trace);
+void dis_grid_aggregate(const dis_grid *g, const dis_params *p, dis_real *flowout);
 /* the same with a complementary grid cg (SetComplGrid, patchgrid.cpp:92-95): after g's own patches, every patch of cg is
  * splatted at its MOVED position with bilinear weights and reversed flow (patchgrid.cpp:278-375).  cg may be NULL. */
-void dis_grid_aggregate_fb(const dis_grid *g, const dis_grid *cg, const dis_params *p, float *flowout);
+void dis_grid_aggregate_fb(const dis_grid *g, const dis_grid *cg, const dis_params *p, dis_real *flowout);
 
 /* ---- variational refinement (kroeger/refine_variational.cpp + FDF1.0.1) ----
  * planar images have stride = ceil4(w) like image_new (image.c:15-31). */
 int dis_stride(int w);
-void dis_image_warp(float *dst, float *mask, const float *src, const float *wx, const float *wy,
+void dis_image_warp(dis_real *dst, dis_real *mask, const dis_real *src, const dis_real *wx, const dis_real *wy,
                     int w, int h, int noc);
-void dis_get_derivatives(const float *im1, const float *im2w, int w, int h, int noc,
-                         float *Ix, float *Iy, float *Iz, float *Ixx, float *Ixy, float *Iyy,
-                         float *Ixz, float *Iyz);
-void dis_compute_smoothness(float *horiz, float *vert, const float *uu, const float *vv,
-                            int w, int h, float quarter_alpha);
-void dis_compute_data(float *a11, float *a12, float *a22, float *b1, float *b2,
-                      const float *mask, const float *du, const float *dv,
-                      const float *Ix, const float *Iy, const float *Iz, const float *Ixx,
-                      const float *Ixy, const float *Iyy, const float *Ixz, const float *Iyz,
-                      int w, int h, int noc, float half_delta_over3, float half_gamma_over3);
-void dis_sub_laplacian(float *dst, const float *src, const float *horiz, const float *vert,
+void dis_get_derivatives(const dis_real *im1, const dis_real *im2w, int w, int h, int noc,
+                         dis_real *Ix, dis_real *Iy, dis_real *Iz, dis_real *Ixx, dis_real *Ixy, dis_real *Iyy,
+                         dis_real *Ixz, dis_real *Iyz);
+void dis_compute_smoothness(dis_real *horiz, dis_real *vert, const dis_real *uu, const dis_real *vv,
+                            int w, int h, dis_real quarter_alpha);
+void dis_compute_data(dis_real *a11, dis_real *a12, dis_real *a22, dis_real *b1, dis_real *b2,
+                      const dis_real *mask, const dis_real *du, const dis_real *dv,
+                      const dis_real *Ix, const dis_real *Iy, const dis_real *Iz, const dis_real *Ixx,
+                      const dis_real *Ixy, const dis_real *Iyy, const dis_real *Ixz, const dis_real *Iyz,
+                      int w, int h, int noc, dis_real half_delta_over3, dis_real half_gamma_over3);
+void dis_sub_laplacian(dis_real *dst, const dis_real *src, const dis_real *horiz, const dis_real *vert,
                        int w, int h);
-void dis_sor_coupled(float *du, float *dv, float *a11, float *a12, float *a22, const float *b1,
-                     const float *b2, const float *horiz, const float *vert, int w, int h,
-                     int iterations, float omega);
+void dis_sor_coupled(dis_real *du, dis_real *dv, dis_real *a11, dis_real *a12, dis_real *a22, const dis_real *b1,
+                     const dis_real *b2, const dis_real *horiz, const dis_real *vert, int w, int h,
+                     int iterations, dis_real omega);
 /* red-black ordering of the same 2x2 block update (throughput mode of the engine; NOT reference) */
 /* FDF1.0.1/solver.c:19-72 sor_coupled_slow_but_readable, serial rows (a11 / a12 / a22 are read only) */
-void dis_sor_coupled_slow(float *du, float *dv, const float *a11, const float *a12, const float *a22, const float *b1,
-                          const float *b2, const float *horiz, const float *vert, int w, int h, int iterations, float omega);
-void dis_sor_coupled_redblack(float *du, float *dv, float *a11, float *a12, float *a22,
-                              const float *b1, const float *b2, const float *horiz,
-                              const float *vert, int w, int h, int iterations, float omega);
+void dis_sor_coupled_slow(dis_real *du, dis_real *dv, const dis_real *a11, const dis_real *a12, const dis_real *a22, const dis_real *b1,
+                          const dis_real *b2, const dis_real *horiz, const dis_real *vert, int w, int h, int iterations, dis_real omega);
+void dis_sor_coupled_redblack(dis_real *du, dis_real *dv, dis_real *a11, dis_real *a12, dis_real *a22,
+                              const dis_real *b1, const dis_real *b2, const dis_real *horiz,
+                              const dis_real *vert, int w, int h, int iterations, dis_real omega);
 /* whole VarRefClass ctor: I0/I1 padded level images, flow w x h x 2 interleaved, in place */
-void dis_varref(const float *I0, const float *I1, int w, int h, int lvl, const dis_params *p,
-                float *flow, int sor_mode /*0 lexicographic sor_coupled (reference default build), 1 red-black, 2 sor_coupled_slow_but_readable (reference OpenMP build, serial)*/);
+void dis_varref(const dis_real *I0, const dis_real *I1, int w, int h, int lvl, const dis_params *p,
+                dis_real *flow, int sor_mode /*0 lexicographic sor_coupled (reference default build), 1 red-black, 2 sor_coupled_slow_but_readable (reference OpenMP build, serial)*/);
 /* stereo depth (SELECTMODE 2): compute_data_DE (opticalflow_aux.c:446-540), sor_coupled_slow_but_readable_DE
  * (solver.c:428-466, serial = lexicographic Gauss-Seidel) and RefLevelDE (refine_variational.cpp:243-330);
  * flow is w x h x 1, camlr selects the sign clamp of the update (:299-314) */
-void dis_compute_data_de(float *a11, float *b1, const float *mask, const float *du,
-                         const float *Ix, const float *Iy, const float *Iz, const float *Ixx,
-                         const float *Ixy, const float *Iyy, const float *Ixz, const float *Iyz,
-                         int w, int h, int noc, float half_delta_over3, float half_gamma_over3);
-void dis_sor_de(float *du, const float *a11, const float *b1, const float *horiz, const float *vert,
-                int w, int h, int iterations, float omega);
-void dis_varref_depth(const float *I0, const float *I1, int w, int h, int lvl, const dis_params *p,
-                      float *flow, int camlr);
+void dis_compute_data_de(dis_real *a11, dis_real *b1, const dis_real *mask, const dis_real *du,
+                         const dis_real *Ix, const dis_real *Iy, const dis_real *Iz, const dis_real *Ixx,
+                         const dis_real *Ixy, const dis_real *Iyy, const dis_real *Ixz, const dis_real *Iyz,
+                         int w, int h, int noc, dis_real half_delta_over3, dis_real half_gamma_over3);
+void dis_sor_de(dis_real *du, const dis_real *a11, const dis_real *b1, const dis_real *horiz, const dis_real *vert,
+                int w, int h, int iterations, dis_real omega);
+void dis_varref_depth(const dis_real *I0, const dis_real *I1, int w, int h, int lvl, const dis_params *p,
+                      dis_real *flow, int camlr);
 
 /* ---- whole flow: OFClass ctor (kroeger/oflow.cpp:32-363) on prebuilt pyramids ---- */
 /* flows (initflow, outflow, level_dump) have 2 channels, or 1 in depth mode */
 void dis_flow_pyr(const dis_pyramid *P0, const dis_pyramid *P1, const dis_params *p,
-                  const float *initflow, float *outflow, int sor_mode,
-                  float *level_dump /* optional: concatenated pre/post-refinement flows */);
+                  const dis_real *initflow, dis_real *outflow, int sor_mode,
+                  dis_real *level_dump /* optional: concatenated pre/post-refinement flows */);
 /* convenience: padded frames in -> finest-scale flow out (pyramid + flow) */
-void dis_flow(const float *I0, const float *I1, int wp, int hp, const dis_params *p,
-              float *outflow, int sor_mode);
+void dis_flow(const dis_real *I0, const dis_real *I1, int wp, int hp, const dis_params *p,
+              dis_real *outflow, int sor_mode);
 /* bench.py's cpu_baseline, all-cores leg: n_total pairs (pair k = source pair k % nsrc of the unpadded w x h x noc frames)
  * frame-parallel on nthreads pthreads with thread-private block caches (no allocation per pair after a thread's first);
  * with_pyramid 1: padding + pyramids + flow per pair, 0: flow on pyramids built once per thread.  out (optional): the flows
  * of pairs 0 .. min(n_total, nsrc)-1.  Returns the seconds the n_total pairs took (every thread runs one untimed pair first). */
-double dis_flow_many(const float *I0, const float *I1, long pair_stride, int nsrc, int w, int h, const dis_params *p,
-                     int n_total, int nthreads, int with_pyramid, float *out);
+double dis_flow_many(const dis_real *I0, const dis_real *I1, long pair_stride, int nsrc, int w, int h, const dis_params *p,
+                     int n_total, int nthreads, int with_pyramid, dis_real *out);
 /* parity-sensitivity switches (tests only): order of the per-patch reductions (definition D1) and of the 2x2 mean (D4) */
 void dis_set_sum_order(int order);
 void dis_set_mean_order(int order);
 /* kroeger/run_dense.cpp:407-414: *2^sc_l, bilinear x2^sc_l (cv::resize INTER_LINEAR), crop */
-void dis_upsample_crop(const float *flow, int wl, int hl, int sc_l, int padw, int padh,
-                       int w_org, int h_org, float *out);
+void dis_upsample_crop(const dis_real *flow, int wl, int hl, int sc_l, int padw, int padh,
+                       int w_org, int h_org, dis_real *out);
 /* the same for nch interleaved channels (depth mode: 1, run_dense.cpp:387-388) */
-void dis_upsample_crop_n(const float *flow, int wl, int hl, int sc_l, int padw, int padh,
-                         int w_org, int h_org, int nch, float *out);
+void dis_upsample_crop_n(const dis_real *flow, int wl, int hl, int sc_l, int padw, int padh,
+                         int w_org, int h_org, int nch, dis_real *out);
 
 #ifdef __cplusplus
 }

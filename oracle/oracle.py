@@ -11,41 +11,57 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_LIB64 = None
 
 f32p = C.POINTER(C.c_float)
 
 
-class DisParams(C.Structure):
-    """mirror of struct dis_params (oracle/dis_oracle.h) == optparam of kroeger/oflow.h:33-76"""
-    _fields_ = [("sc_f", C.c_int), ("sc_l", C.c_int), ("ps", C.c_int), ("max_iter", C.c_int),
-                ("min_iter", C.c_int), ("dp_thresh", C.c_float), ("dr_thresh", C.c_float),
-                ("res_thresh", C.c_float), ("patove", C.c_float), ("patnorm", C.c_int),
-                ("noc", C.c_int), ("usetvref", C.c_int), ("tv_alpha", C.c_float),
-                ("tv_gamma", C.c_float), ("tv_delta", C.c_float), ("tv_innerit", C.c_int),
-                ("tv_solverit", C.c_int), ("tv_sor", C.c_float),
-                ("costfct", C.c_int), ("normoutlier", C.c_float), ("usefbcon", C.c_int), ("depth", C.c_int)]
+f64p = C.POINTER(C.c_double)
 
 
-class DisPyramid(C.Structure):
-    _fields_ = [("nlev", C.c_int), ("noc", C.c_int), ("ps", C.c_int), ("w0", C.c_int), ("h0", C.c_int),
-                ("im", C.POINTER(f32p)), ("dx", C.POINTER(f32p)), ("dy", C.POINTER(f32p))]
+def _mirrors(real):
+    """the ctypes mirrors of dis_params, dis_pyramid and dis_grid (oracle/dis_oracle.h) for one dis_real"""
+    rp = C.POINTER(real)
+
+    class DisParams(C.Structure):
+        """mirror of struct dis_params (oracle/dis_oracle.h) == optparam of kroeger/oflow.h:33-76"""
+        _fields_ = [("sc_f", C.c_int), ("sc_l", C.c_int), ("ps", C.c_int), ("max_iter", C.c_int),
+                    ("min_iter", C.c_int), ("dp_thresh", real), ("dr_thresh", real),
+                    ("res_thresh", real), ("patove", real), ("patnorm", C.c_int),
+                    ("noc", C.c_int), ("usetvref", C.c_int), ("tv_alpha", real),
+                    ("tv_gamma", real), ("tv_delta", real), ("tv_innerit", C.c_int),
+                    ("tv_solverit", C.c_int), ("tv_sor", real),
+                    ("costfct", C.c_int), ("normoutlier", real), ("usefbcon", C.c_int), ("depth", C.c_int)]
+
+    class DisPyramid(C.Structure):
+        _fields_ = [("nlev", C.c_int), ("noc", C.c_int), ("ps", C.c_int), ("w0", C.c_int), ("h0", C.c_int),
+                    ("im", C.POINTER(rp)), ("dx", C.POINTER(rp)), ("dy", C.POINTER(rp))]
+
+    class DisGrid(C.Structure):
+        _fields_ = [("w", C.c_int), ("h", C.c_int), ("ps", C.c_int), ("noc", C.c_int), ("steps", C.c_int),
+                    ("nopw", C.c_int), ("noph", C.c_int), ("nop", C.c_int), ("pad", C.c_int),
+                    ("tmp_w", C.c_int), ("lvl", C.c_int), ("lb", real), ("ubw", real),
+                    ("ubh", real), ("pt_ref", rp), ("p_init", rp), ("tmpl", rp), ("tdx", rp),
+                    ("tdy", rp), ("hes", rp), ("p_iter", rp), ("pweight", rp),
+                    ("cnt", C.POINTER(C.c_int)), ("depth", C.c_int), ("camlr", C.c_int)]
+
+    return DisParams, DisPyramid, DisGrid
 
 
-class DisGrid(C.Structure):
-    _fields_ = [("w", C.c_int), ("h", C.c_int), ("ps", C.c_int), ("noc", C.c_int), ("steps", C.c_int),
-                ("nopw", C.c_int), ("noph", C.c_int), ("nop", C.c_int), ("pad", C.c_int),
-                ("tmp_w", C.c_int), ("lvl", C.c_int), ("lb", C.c_float), ("ubw", C.c_float),
-                ("ubh", C.c_float), ("pt_ref", f32p), ("p_init", f32p), ("tmpl", f32p), ("tdx", f32p),
-                ("tdy", f32p), ("hes", f32p), ("p_iter", f32p), ("pweight", f32p),
-                ("cnt", C.POINTER(C.c_int)), ("depth", C.c_int), ("camlr", C.c_int)]
+DisParams, DisPyramid, DisGrid = _mirrors(C.c_float)
+# the -DDIS_REAL_DOUBLE build (libdis_oracle_f64.so): every dis_real is a double
+DisParams64, DisPyramid64, DisGrid64 = _mirrors(C.c_double)
 
 
 def build(force=False):
-    """compile oracle/libdis_oracle.so (and oracle/_ref when the reference tree is present)"""
+    """compile oracle/libdis_oracle.so, its double-precision build libdis_oracle_f64.so (and oracle/_ref when the reference tree
+    is present)"""
     so = os.path.join(_HERE, "libdis_oracle.so")
-    src = os.path.join(_HERE, "dis_oracle.c")
-    if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.check_call(["make", "-C", _HERE, "libdis_oracle.so"], stdout=subprocess.DEVNULL)
+    newest = max(os.path.getmtime(os.path.join(_HERE, f)) for f in ("dis_oracle.c", "dis_oracle.h"))
+    for name in ("libdis_oracle.so", "libdis_oracle_f64.so"):
+        lib_path = os.path.join(_HERE, name)
+        if force or not os.path.exists(lib_path) or os.path.getmtime(lib_path) < newest:
+            subprocess.check_call(["make", "-C", _HERE, name], stdout=subprocess.DEVNULL)
     if os.path.isdir("/root/reference/kroeger/FDF1.0.1"):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
     return so
@@ -66,24 +82,38 @@ def use_native():
     return "gcc -O3 -msse4 -march=native -ffp-contract=off"
 
 
+def _load(so_name, real, pyramid, grid):
+    """load one build of dis_oracle.c and declare the signatures that pass or return a dis_real by value"""
+    so = os.path.join(_HERE, so_name)
+    if not os.path.exists(so):
+        build()
+    rp = C.POINTER(real)
+    L = C.CDLL(so)
+    L.dis_pyramid_build.restype = C.POINTER(pyramid)
+    L.dis_grid_new.restype = C.POINTER(grid)
+    L.dis_sum.restype = real
+    L.dis_sum.argtypes = [rp, C.c_int, C.c_int]
+    L.dis_compute_smoothness.argtypes = [rp, rp, rp, rp, C.c_int, C.c_int, real]
+    L.dis_compute_data.argtypes = [rp] * 16 + [C.c_int, C.c_int, C.c_int, real, real]
+    L.dis_sor_coupled.argtypes = [rp] * 9 + [C.c_int, C.c_int, C.c_int, real]
+    L.dis_sor_coupled_redblack.argtypes = L.dis_sor_coupled.argtypes
+    L.dis_sor_coupled_slow.argtypes = L.dis_sor_coupled.argtypes
+    return L
+
+
 def lib():
     global _LIB
     if _LIB is None:
-        so = os.path.join(_HERE, _SO_NAME)
-        if not os.path.exists(so):
-            build()
-        L = C.CDLL(so)
-        L.dis_pyramid_build.restype = C.POINTER(DisPyramid)
-        L.dis_grid_new.restype = C.POINTER(DisGrid)
-        L.dis_sum.restype = C.c_float
-        L.dis_sum.argtypes = [f32p, C.c_int, C.c_int]
-        L.dis_compute_smoothness.argtypes = [f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_float]
-        L.dis_compute_data.argtypes = [f32p] * 16 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
-        L.dis_sor_coupled.argtypes = [f32p] * 9 + [C.c_int, C.c_int, C.c_int, C.c_float]
-        L.dis_sor_coupled_redblack.argtypes = L.dis_sor_coupled.argtypes
-        L.dis_sor_coupled_slow.argtypes = L.dis_sor_coupled.argtypes
-        _LIB = L
+        _LIB = _load(_SO_NAME, C.c_float, DisPyramid, DisGrid)
     return _LIB
+
+
+def lib64():
+    """the double-precision build (see the f64 front end below)"""
+    global _LIB64
+    if _LIB64 is None:
+        _LIB64 = _load("libdis_oracle_f64.so", C.c_double, DisPyramid64, DisGrid64)
+    return _LIB64
 
 
 def P(a):
@@ -156,13 +186,28 @@ class Pyramid:
 
 
 class Grid:
+    # the precision of this front end: Grid64 below overrides the three
+    _real = np.float32
+    _lib = staticmethod(lib)
+    _rp = f32p
+
+    def _a(self, a):
+        return np.ascontiguousarray(a, dtype=self._real)
+
+    def _p(self, a):
+        return a.ctypes.data_as(self._rp)
+
+    def _params(self, params):
+        return params
+
     def __init__(self, w, h, lvl, params, camlr=0):
-        self.params = params
-        self.ptr = lib().dis_grid_new(w, h, lvl, C.byref(params))
+        self.params = params = self._params(params)
+        self.ptr = self._lib().dis_grid_new(w, h, lvl, C.byref(params))
         self.ptr.contents.camlr = camlr
         self.np = 1 if params.depth else 2
         g = self.ptr.contents
         self.nop, self.nopw, self.noph, self.steps = g.nop, g.nopw, g.noph, g.steps
+        self.lb, self.ubw, self.ubh = g.lb, g.ubw, g.ubh
         self.nv = params.ps * params.ps * params.noc
         self.w, self.h = w, h
 
@@ -170,29 +215,29 @@ class Grid:
         return np.ctypeslib.as_array(ptr, shape=shape)
 
     def init(self, I0, I0x, I0y):
-        self._keep = (f32(I0), f32(I0x), f32(I0y))
-        lib().dis_grid_init(self.ptr, C.byref(self.params), *[P(a) for a in self._keep])
+        self._keep = (self._a(I0), self._a(I0x), self._a(I0y))
+        self._lib().dis_grid_init(self.ptr, C.byref(self.params), *[self._p(a) for a in self._keep])
 
     def init_from_coarser(self, flow_prev):
-        fp = f32(flow_prev)
-        lib().dis_grid_init_from_coarser(self.ptr, P(fp))
+        fp = self._a(flow_prev)
+        self._lib().dis_grid_init_from_coarser(self.ptr, self._p(fp))
 
     def optimize(self, I1, trace=False):
-        I1 = f32(I1)
+        I1 = self._a(I1)
         tr = None
         if trace:
-            tr = np.zeros((self.nop, self.params.max_iter + 1, 4), np.float32)
-        lib().dis_grid_optimize(self.ptr, C.byref(self.params), P(I1), P(tr) if trace else None)
+            tr = np.zeros((self.nop, self.params.max_iter + 1, 4), self._real)
+        self._lib().dis_grid_optimize(self.ptr, C.byref(self.params), self._p(I1), self._p(tr) if trace else None)
         return tr
 
     def aggregate(self):
-        out = np.zeros((self.h, self.w, self.np), np.float32)
-        lib().dis_grid_aggregate(self.ptr, C.byref(self.params), P(out))
+        out = np.zeros((self.h, self.w, self.np), self._real)
+        self._lib().dis_grid_aggregate(self.ptr, C.byref(self.params), self._p(out))
         return out
 
     def aggregate_fb(self, cg):
-        out = np.zeros((self.h, self.w, self.np), np.float32)
-        lib().dis_grid_aggregate_fb(self.ptr, cg.ptr, C.byref(self.params), P(out))
+        out = np.zeros((self.h, self.w, self.np), self._real)
+        self._lib().dis_grid_aggregate_fb(self.ptr, cg.ptr, C.byref(self.params), self._p(out))
         return out
 
     @property
@@ -216,7 +261,7 @@ class Grid:
 
     def __del__(self):
         try:
-            lib().dis_grid_free(self.ptr)
+            self._lib().dis_grid_free(self.ptr)
         except Exception:
             pass
 
@@ -225,6 +270,47 @@ def varref(I0_lvl, I1_lvl, w, h, lvl, params, flow, sor_mode=0):
     flow = f32(flow).copy()
     a, b = f32(I0_lvl), f32(I1_lvl)
     lib().dis_varref(P(a), P(b), w, h, lvl, C.byref(params), P(flow), int(sor_mode))
+    return flow
+
+
+# ---- the f64 front end: the same source compiled with double as its real type (oracle/Makefile, libdis_oracle_f64.so).  It takes
+# the f32 front end's arguments -- float32 arrays, a DisParams -- and widens them, so both builds solve the same problem from the
+# same inputs; results come back as float64.  The yardstick of the tolerance-mode tests (tests/fast_ref.py), never a parity
+# reference.
+
+def f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def P64(a):
+    return a.ctypes.data_as(f64p)
+
+
+def params64(p):
+    """a DisParams widened field by field (every real keeps its f32 value)"""
+    if isinstance(p, DisParams64):
+        return p
+    q = DisParams64()
+    for name, _ in DisParams._fields_:
+        setattr(q, name, getattr(p, name))
+    return q
+
+
+class Grid64(Grid):
+    """Grid on the double-precision build: init / init_from_coarser / optimize / aggregate and every state array in f64"""
+    _real = np.float64
+    _lib = staticmethod(lib64)
+    _rp = f64p
+
+    def _params(self, params):
+        return params64(params)
+
+
+def varref64(I0_lvl, I1_lvl, w, h, lvl, params, flow, sor_mode=0):
+    """varref() on the double-precision build: float32 level images and flow in, the refined flow in float64 out"""
+    flow = f64(flow).copy()
+    a, b = f64(I0_lvl), f64(I1_lvl)
+    lib64().dis_varref(P64(a), P64(b), w, h, lvl, C.byref(params64(params)), P64(flow), int(sor_mode))
     return flow
 
 
