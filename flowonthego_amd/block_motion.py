@@ -32,39 +32,26 @@ def main(argv=None):
     if not 0 <= a.refine <= 3:
         ap.error("--refine must be 0 .. 3")
     import numpy as np
-    import torch
+    from ._cli import (array_like_array, flow_like_flow, frame_like_flow, load_array, load_flow, occlusion_mask, refusing, save_frame_png,
+                       to_device)
     from .blockmotion import block_motion
-    from .color import write_png
-    from .flo import read_flo
-    try:
-        flow = read_flo(a.flow)
-        bw = None if a.bw is None else read_flo(a.bw)
-        cur, ref = np.load(a.cur), np.load(a.ref)
-    except (OSError, ValueError) as e:
-        sys.stderr.write("block_motion: %s\n" % e)
+    with refusing("block_motion") as inputs:
+        flow = load_flow(a.flow)
+        h, w = flow.shape[:2]
+        bw = flow_like_flow(load_flow(a.bw), a.bw, flow, a.flow)
+        cur = frame_like_flow(load_array(a.cur), a.cur, h, w, ("uint8",))
+        ref = array_like_array(frame_like_flow(load_array(a.ref), a.ref, h, w, ("uint8",)), a.ref, cur, a.cur)
+    if inputs.refused:
         return 1
-    h, w = flow.shape[:2]
-    for nm, f in ((a.cur, cur), (a.ref, ref)):
-        if f.dtype != np.uint8 or f.shape not in ((h, w), (h, w, 1), (h, w, 3)) or f.shape != cur.shape:
-            sys.stderr.write("block_motion: %s must hold an (%d, %d) or (%d, %d, 3) uint8 array, the same for both frames\n"
-                             % (nm, h, w, h, w))
-            return 1
-    if bw is not None and bw.shape != flow.shape:
-        sys.stderr.write("block_motion: %s is %dx%d, %s is %dx%d\n" % (a.flow, w, h, a.bw, bw.shape[1], bw.shape[0]))
-        return 1
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    f, mask = dev(flow), None
-    if bw is not None:
-        from .consistency import fb_check
-        mask = fb_check(f, dev(bw))[0]
-    mv, cost, kind, pred, st = block_motion(dev(cur), dev(ref), f, mask=mask, block=a.block, refine=a.refine, pred=True, stats=True)
+    f = to_device(flow)
+    mask = occlusion_mask(f, to_device(bw))
+    mv, cost, kind, pred, st = block_motion(to_device(cur), to_device(ref), f, mask=mask, block=a.block, refine=a.refine, pred=True, stats=True)
     st = st.cpu().numpy()
     np.savez(a.out, mv=mv.cpu().numpy(), cost=cost.cpu().numpy(), kind=kind.cpu().numpy())
     psnr = float("inf") if st[2] == 0 else 10.0 * math.log10(255.0 ** 2 * cur.size / float(st[2]))
     print("SAD %d  zero-vector SAD %d  prediction PSNR %.2f dB" % (st[0], st[1], psnr))
     if a.pred:
-        p = pred.cpu().numpy().reshape(h, w, -1)
-        write_png(a.pred, np.repeat(p, 3, axis=2) if p.shape[2] == 1 else p)
+        save_frame_png(a.pred, pred, h, w)
     return 0
 
 

@@ -21,31 +21,27 @@ def main(argv=None):
     if a.bw is not None and len(a.bw) != len(paths):
         ap.error("--bw needs as many flows as the forward sequence (%d)" % len(paths))
     import numpy as np
-    import torch
+    from ._cli import Refusal, flow_like_flow, load_array, load_flow, refusing, to_device
     from .chain import STATS, chain, track_points
-    from .flo import read_flo, write_flo
-    try:
-        fw = [read_flo(p) for p in paths]
-        bw = [read_flo(p) for p in a.bw] if a.bw else None
-        pts = np.load(a.points[0]) if a.points else None
-    except (OSError, ValueError) as e:
-        sys.stderr.write("chain_flow: %s\n" % e)
+    from .flo import write_flo
+    with refusing("chain_flow") as inputs:
+        fw = [load_flow(p) for p in paths]
+        bw = [load_flow(p) for p in a.bw] if a.bw else None
+        h, w = fw[0].shape[:2]
+        for f, p in zip(fw[1:] + (bw or []), paths[1:] + (a.bw or [])):
+            flow_like_flow(f, p, fw[0], paths[0])
+        pts = load_array(a.points[0]) if a.points else None
+        if pts is not None and (pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 1 or pts.dtype != np.float32):
+            raise Refusal("%s must hold a (P, 2) float32 array" % a.points[0])
+    if inputs.refused:
         return 1
-    h, w = fw[0].shape[:2]
-    if any(f.shape != (h, w, 2) for f in fw + (bw or [])):
-        sys.stderr.write("chain_flow: every flow must be %d x %d, the size of %s\n" % (w, h, paths[0]))
-        return 1
-    if pts is not None and (pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 1 or pts.dtype != np.float32):
-        sys.stderr.write("chain_flow: %s must hold a (P, 2) float32 array\n" % a.points[0])
-        return 1
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    F, B = dev(np.stack(fw)), None if bw is None else dev(np.stack(bw))
+    F, B = to_device(np.stack(fw)), None if bw is None else to_device(np.stack(bw))
     total, _, _, st = chain(F, B, stats=True)
     st = st.cpu().numpy()
     print("  ".join("%s %.4f" % (nm, c / (h * w)) for nm, c in zip(STATS[:4], st[:4])) + "  mean_steps %.4f" % (st[4] / (h * w)))
     write_flo(out, total.cpu().numpy())
     if pts is not None:
-        traj, _, _ = track_points(dev(pts), F, B)
+        traj, _, _ = track_points(to_device(pts), F, B)
         np.save(a.points[1], traj.cpu().numpy())
     return 0
 

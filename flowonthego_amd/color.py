@@ -1,15 +1,14 @@
 """Middlebury flow colour code on the GPU (flow_code/C/color_flow.cpp MotionToColor + colorcode.cpp computeColor of the reference
-tree) over fotg_flow_color / fotg_upsample_crop_color of libfotg.so, a stdlib-only PNG writer and the legend image of colortest.cpp.
+tree) over fotg_flow_color / fotg_upsample_crop_color of libfotg.so, and the legend image of colortest.cpp (the PNG writer: _png.py).
 The colour code runs in HIP only; there is no CPU fallback.  Output is uint8 R, G, B per pixel, normalised per image."""
 import ctypes as C
-import struct
-import zlib
 
 import numpy as np
 import torch
 
 from ._args import _dev_f32, _ptr, _stream, coarse_flow, coarse_shape, dense_flow
 from ._lib import check, lib
+from ._png import write_png  # noqa: F401  (its place before _png.py; still importable from here)
 
 
 def _maxmotion(maxmotion):
@@ -44,26 +43,6 @@ def upsample_crop_color(ofc, flow, maxmotion=None, out=None, stats=False):
     st = torch.empty((n, 5), dtype=torch.float32, device=ofc.device)
     check(lib().fotg_upsample_crop_color(ofc._h, n, _ptr(flow), _maxmotion(maxmotion), _ptr(rgb), _ptr(st), _stream(ofc.device)))
     return (rgb, st) if stats else rgb
-
-
-def write_png(path, rgb):
-    """rgb: (h, w, 3) uint8 (numpy or tensor) -> an 8-bit RGB PNG (zlib + struct only)"""
-    if hasattr(rgb, "detach"):
-        rgb = rgb.detach().cpu().numpy()
-    rgb = np.ascontiguousarray(rgb)
-    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.shape[0] < 1 or rgb.shape[1] < 1:
-        raise ValueError("rgb must be a non-empty (h, w, 3) uint8 array, got %s %s" % (rgb.dtype, rgb.shape))
-    h, w = rgb.shape[:2]
-
-    def chunk(tag, data):
-        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
-
-    raw = np.concatenate([np.zeros((h, 1), np.uint8), rgb.reshape(h, w * 3)], axis=1).tobytes()   # filter type 0 per row
-    with open(path, "wb") as f:
-        f.write(b"\x89PNG\r\n\x1a\n")
-        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))
-        f.write(chunk(b"IDAT", zlib.compress(raw, 6)))
-        f.write(chunk(b"IEND", b""))
 
 
 def color_wheel(truerange, size=151, device=0):

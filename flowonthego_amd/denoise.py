@@ -31,37 +31,19 @@ def main(argv=None):
     if not (a.tau > 0 and a.tau < float("inf")):
         ap.error("--tau must be a positive number")
     import numpy as np
-    import torch
-    from . import img_params, operating_point
-    from .oflow import OFClass
-    try:
-        frames = np.load(a.frames)
-        ref = None if a.ref is None else np.load(a.ref)
-    except (OSError, ValueError) as e:
-        sys.stderr.write("denoise: %s\n" % e)
+    from ._cli import array_like_array, drop_c1, frame_sequence, load_array, refusing, sequence_context, to_device
+    with refusing("denoise") as inputs:
+        loaded = frame_sequence(a.frames, 1, "T", c1=True)
+        ref = drop_c1(array_like_array(load_array(a.ref), a.ref, loaded, a.frames))
+    if inputs.refused:
         return 1
-    if frames.ndim not in (3, 4) or frames.shape[0] < 1 or frames.dtype not in (np.uint8, np.float32) or (frames.ndim == 4 and frames.shape[3] not in (1, 3)):
-        sys.stderr.write("denoise: %s must hold a (T, h, w) or (T, h, w, 3) uint8 or float32 array\n" % a.frames)
-        return 1
-    if ref is not None and (ref.shape != frames.shape or ref.dtype != frames.dtype):
-        sys.stderr.write("denoise: %s must have the shape and type of %s\n" % (a.ref, a.frames))
-        return 1
-    shape = frames.shape
-    if frames.ndim == 4 and frames.shape[3] == 1:
-        frames, ref = frames[..., 0], None if ref is None else ref[..., 0]
+    frames = drop_c1(loaded)
     T, h, w = frames.shape[:3]
-    color = frames.ndim == 4
-    u8_rgb = color and frames.dtype == np.uint8          # 8-bit colour frames become gray for the flow; float32 ones are used as RGB
-    op = operating_point(a.op_point, w, 3 if color and not u8_rgb else 1)
-    op.bidir = bool(a.occlusion)
-    if u8_rgb:
-        op.u8_color = 2
     K = 2 * a.radius
-    ofc = OFClass(op, img_params(width=w, height=h), max_batch=K * min(T, 8))
-    dev = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    dst, used, st = ofc.temporal_filter(dev(frames), radius=a.radius, tau=a.tau, occlusion=a.occlusion, ref=dev(ref), stats=True)
+    ofc = sequence_context(frames, a.op_point, bidir=a.occlusion, max_batch=K * min(T, 8))
+    dst, used, st = ofc.temporal_filter(to_device(frames), radius=a.radius, tau=a.tau, occlusion=a.occlusion, ref=to_device(ref), stats=True)
     out = dst.cpu().numpy()
-    np.save(a.out, out.reshape(shape))
+    np.save(a.out, out.reshape(loaded.shape))
     if ref is not None:
         print("PSNR before %.3f dB  after %.3f dB" % (_psnr(frames, ref), _psnr(out, ref)))
     print("mean used %.4f of %d neighbours" % (float(st[:, 0].sum().item()) / (T * h * w), K))

@@ -15,19 +15,15 @@ def main(argv=None):
     ap.add_argument("--alpha1", type=float, default=0.01)
     ap.add_argument("--alpha2", type=float, default=0.5)
     a = ap.parse_args(sys.argv[1:] if argv is None else argv)
-    import torch
-    from .color import write_png
+    from ._cli import flow_like_flow, load_flow, refusing, to_device
+    from ._png import write_png
     from .consistency import CODES, fb_check, mask_to_rgb
-    from .flo import read_flo
-    try:
-        fw, bw = read_flo(a.fw), read_flo(a.bw)
-    except (OSError, ValueError) as e:
-        sys.stderr.write("fb_check: %s\n" % e)
+    with refusing("fb_check") as inputs:
+        fw = load_flow(a.fw)
+        bw = flow_like_flow(load_flow(a.bw), a.bw, fw, a.fw)
+    if inputs.refused:
         return 1
-    if fw.shape != bw.shape:
-        sys.stderr.write("fb_check: %s is %dx%d, %s is %dx%d\n" % (a.fw, fw.shape[1], fw.shape[0], a.bw, bw.shape[1], bw.shape[0]))
-        return 1
-    mask, _, cnt = fb_check(torch.from_numpy(fw).cuda(), torch.from_numpy(bw).cuda(), a.alpha1, a.alpha2, stats=True)
+    mask, _, cnt = fb_check(to_device(fw), to_device(bw), a.alpha1, a.alpha2, stats=True)
     cnt = cnt.cpu().numpy()[0]
     npix = fw.shape[0] * fw.shape[1]
     print("  ".join("%s %.4f" % (nm, float(c) / npix) for nm, c in zip(CODES, cnt)))

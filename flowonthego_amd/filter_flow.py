@@ -15,8 +15,6 @@ import sys
 
 from ._lib import callable_module
 
-CODE_RGB = ((255, 255, 255), (220, 30, 30), (128, 128, 128), (0, 0, 0))
-
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="filter_flow", description=__doc__.splitlines()[3])
@@ -39,37 +37,25 @@ def main(argv=None):
     sigma = a.radius / 2.0 if a.sigma is None else a.sigma
     if not (sigma > 0 and sigma < float("inf")):
         ap.error("--sigma must be a positive number")
-    import numpy as np
-    import torch
-    from .color import write_png
-    from .flo import read_flo, write_flo
+    from ._cli import flow_like_flow, frame_like_flow, load_array, load_flow, occlusion_mask, refusing, save_code_png, to_device
+    from .flo import write_flo
     from .flowfilter import filter_flow
-    try:
-        flow = read_flo(a.flow)
-        bw = None if a.bw is None else read_flo(a.bw)
-        guide = np.load(a.guide)
-    except (OSError, ValueError) as e:
-        sys.stderr.write("filter_flow: %s\n" % e)
+    with refusing("filter_flow") as inputs:
+        flow = load_flow(a.flow)
+        h, w = flow.shape[:2]
+        bw = flow_like_flow(load_flow(a.bw), a.bw, flow, a.flow)
+        guide = frame_like_flow(load_array(a.guide), a.guide, h, w)
+    if inputs.refused:
         return 1
-    h, w = flow.shape[:2]
-    if guide.dtype not in (np.uint8, np.float32) or guide.shape not in ((h, w), (h, w, 1), (h, w, 3)):
-        sys.stderr.write("filter_flow: %s must hold an (%d, %d) or (%d, %d, 3) uint8 or float32 array\n" % (a.guide, h, w, h, w))
-        return 1
-    if bw is not None and bw.shape != flow.shape:
-        sys.stderr.write("filter_flow: %s is %dx%d, %s is %dx%d\n" % (a.flow, w, h, a.bw, bw.shape[1], bw.shape[0]))
-        return 1
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    f, mask = dev(flow), None
-    if bw is not None:
-        from .consistency import fb_check
-        mask = fb_check(f, dev(bw))[0]
-    out, code, st = filter_flow(f, dev(guide), mask=mask, radius=a.radius, sigma=sigma, tau=a.tau, iters=a.iters, stats=True)
+    f = to_device(flow)
+    mask = occlusion_mask(f, to_device(bw))
+    out, code, st = filter_flow(f, to_device(guide), mask=mask, radius=a.radius, sigma=sigma, tau=a.tau, iters=a.iters, stats=True)
     st = st.cpu().numpy()
     write_flo(a.out, out)
     print("filtered %.4f  filled %.4f  unsupported %.4f  mean change %.4f px"
           % (st[0] / (h * w), st[1] / (h * w), st[2] / (h * w), st[3] / max(2.0 * st[0], 1.0)))
     if a.code:
-        write_png(a.code, np.array(CODE_RGB, np.uint8)[code.cpu().numpy()])
+        save_code_png(a.code, code)
     return 0
 
 

@@ -20,37 +20,29 @@ def main(argv=None):
     a = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if not 0.0 < a.t < 1.0:
         ap.error("t must lie strictly between 0 and 1")
-    import numpy as np
-    import torch
     from . import img_params, operating_point
-    from .color import write_png
+    from ._cli import Refusal, array_like_array, load_array, refusing, save_frame_png, to_device
     from .interp import STATS
     from .oflow import OFClass
-    try:
-        f0, f1 = np.load(a.f0), np.load(a.f1)
-        ref = np.load(a.ref) if a.ref else None
-    except (OSError, ValueError) as e:
-        sys.stderr.write("interp_frame: %s\n" % e)
-        return 1
-    if f0.ndim != 2 or f0.shape != f1.shape or f0.dtype != f1.dtype or f0.dtype not in (np.uint8, np.float32) \
-            or (ref is not None and (ref.shape != f0.shape or ref.dtype != f0.dtype)):
-        sys.stderr.write("interp_frame: the frames must be alike (h, w) uint8 or float32 arrays\n")
+    with refusing("interp_frame") as inputs:
+        f0 = load_array(a.f0)
+        if f0.ndim != 2 or str(f0.dtype) not in ("uint8", "float32"):
+            raise Refusal("%s must hold an (h, w) uint8 or float32 array" % a.f0)
+        f1 = array_like_array(load_array(a.f1), a.f1, f0, a.f0)
+        ref = array_like_array(load_array(a.ref), a.ref, f0, a.f0)
+    if inputs.refused:
         return 1
     h, w = f0.shape
     op = operating_point(a.op, w, 1)
     op.bidir = True
     ofc = OFClass(op, img_params(width=w, height=h))
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    dst, _, st = ofc.interpolate(dev(f0), dev(f1), a.t, ref=None if ref is None else dev(ref), stats=True)
+    dst, _, st = ofc.interpolate(to_device(f0), to_device(f1), a.t, ref=to_device(ref), stats=True)
     st = st.cpu().numpy()
     line = "  ".join("%s %.4f" % (nm, c / (h * w)) for nm, c in zip(STATS[:4], st[:4]))
     if ref is not None:
         line += "  mad_interpolated %.4f  mad_blend %.4f" % (st[4] / (h * w), st[5] / (h * w))
     print(line)
-    img = dst.cpu().numpy().reshape(h, w, 1)
-    if img.dtype != np.uint8:
-        img = np.clip(np.rint(np.nan_to_num(img)), 0, 255).astype(np.uint8)
-    write_png(a.out, np.ascontiguousarray(np.broadcast_to(img, (h, w, 3))))
+    save_frame_png(a.out, dst, h, w)
     ofc.close()
     return 0
 

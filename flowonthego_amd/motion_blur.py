@@ -13,33 +13,22 @@ with the forward-backward check) and out.npy gets frames 0 .. T-1 blurred, same 
 The module is callable: flowonthego_amd.motion_blur(frame, flow, ...) is flowonthego_amd.motionblur.motion_blur(frame, flow, ...)."""
 import argparse
 import sys
-import zlib
 
 from ._lib import callable_module
 
 CODE_RGB = ((0, 0, 0), (255, 255, 255), (220, 30, 30), (128, 128, 128))
 
 
-def _sequence(a, np, torch):
-    from . import img_params, operating_point
-    from .oflow import OFClass
-    try:
-        frames = np.load(a.files[0])
-    except (OSError, ValueError) as e:
-        sys.stderr.write("motion_blur: %s\n" % e)
-        return 1
-    if frames.ndim not in (3, 4) or frames.shape[0] < 2 or frames.dtype not in (np.uint8, np.float32) or (frames.ndim == 4 and frames.shape[3] != 3):
-        sys.stderr.write("motion_blur: %s must hold a (T+1, h, w) or (T+1, h, w, 3) uint8 or float32 array of at least two frames\n" % a.files[0])
+def _sequence(a):
+    import numpy as np
+    from ._cli import frame_sequence, refusing, sequence_context, to_device
+    with refusing("motion_blur") as inputs:
+        frames = frame_sequence(a.files[0], 2, "T+1", c1=False)
+    if inputs.refused:
         return 1
     T, h, w = frames.shape[0] - 1, frames.shape[1], frames.shape[2]
-    color = frames.ndim == 4
-    u8_rgb = color and frames.dtype == np.uint8          # 8-bit colour frames become gray for the flow; float32 ones are used as RGB
-    op = operating_point(a.op_point, w, 3 if color and not u8_rgb else 1)
-    op.bidir = bool(a.occlusion)
-    if u8_rgb:
-        op.u8_color = 2
-    ofc = OFClass(op, img_params(width=w, height=h), max_batch=min(T, 8))
-    out = ofc.motion_blur(torch.from_numpy(np.ascontiguousarray(frames)).cuda(), a.shutter, a.max_blur, occlusion=a.occlusion)
+    ofc = sequence_context(frames, a.op_point, bidir=a.occlusion, max_batch=min(T, 8))
+    out = ofc.motion_blur(to_device(frames), a.shutter, a.max_blur, occlusion=a.occlusion)
     np.save(a.files[1], out.cpu().numpy())
     ofc.close()
     print("%d frames of %d x %d blurred, shutter %g" % (T, w, h, a.shutter))
@@ -66,36 +55,22 @@ def main(argv=None):
         ap.error("--mask and --code belong to the single-frame form")
     if len(a.files) == 3 and a.occlusion:
         ap.error("--occlusion belongs to the sequence form")
-    import numpy as np
-    import torch
     if len(a.files) == 2:
-        return _sequence(a, np, torch)
-    from .color import write_png
-    from .fit_motion import read_gray_png
-    from .flo import read_flo
+        return _sequence(a)
+    from ._cli import frame_like_flow, load_array, load_flow, load_mask_png, mask_like_flow, refusing, save_code_png, save_frame_png, to_device
     from .motionblur import motion_blur
-    try:
-        frame, flow = np.load(a.files[0]), read_flo(a.files[1])
-        mask = read_gray_png(a.mask) if a.mask else None
-    except (OSError, ValueError, zlib.error) as e:
-        sys.stderr.write("motion_blur: %s\n" % e)
+    with refusing("motion_blur") as inputs:
+        flow = load_flow(a.files[1])
+        h, w = flow.shape[:2]
+        frame = frame_like_flow(load_array(a.files[0]), a.files[0], h, w)
+        mask = mask_like_flow(load_mask_png(a.mask), a.mask, h, w)
+    if inputs.refused:
         return 1
-    h, w = flow.shape[:2]
-    if frame.dtype not in (np.uint8, np.float32) or frame.shape[:2] != (h, w) or frame.shape[2:] not in ((), (1,), (3,)):
-        sys.stderr.write("motion_blur: %s must hold a (%d, %d[, 3]) uint8 or float32 array (the flow's size)\n" % (a.files[0], h, w))
-        return 1
-    if mask is not None and mask.shape != (h, w):
-        sys.stderr.write("motion_blur: %s is %d x %d, the flow %d x %d\n" % (a.mask, mask.shape[1], mask.shape[0], w, h))
-        return 1
-    dev = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    dst, code, st = motion_blur(dev(frame), dev(flow), dev(mask), a.shutter, a.max_blur, code=True, stats=True)
+    dst, code, st = motion_blur(to_device(frame), to_device(flow), to_device(mask), a.shutter, a.max_blur, code=True, stats=True)
     st = st.cpu().numpy()
-    img = dst.cpu().numpy().reshape(h, w, -1)
-    if img.dtype != np.uint8:
-        img = np.clip(np.rint(np.nan_to_num(img)), 0, 255).astype(np.uint8)
-    write_png(a.files[2], np.ascontiguousarray(np.broadcast_to(img, (h, w, 3))))
+    save_frame_png(a.files[2], dst, h, w)
     if a.code:
-        write_png(a.code, np.array(CODE_RGB, np.uint8)[code.cpu().numpy()])
+        save_code_png(a.code, code, CODE_RGB)
     print("untouched %.4f  blurred %.4f  clamped %.4f  unknown %.4f  taps per pixel %.3f  longest half-streak %.4f px" % (
         st[0] / (h * w), st[1] / (h * w), st[2] / (h * w), st[3] / (h * w), st[4] / (h * w), st[6] / 16.0))
     return 0

@@ -12,7 +12,6 @@ cell.  Prints the image's summed HOF and the share of the admissible pixels in t
 The module is callable: flowonthego_amd.motion_histograms(flow, ...) is flowonthego_amd.histograms.motion_histograms(flow, ...)."""
 import argparse
 import sys
-import zlib
 
 from ._lib import callable_module
 
@@ -36,29 +35,19 @@ def main(argv=None):
     if a.model != "none" and a.model not in MODELS:
         ap.error("--model must be one of none, " + ", ".join(MODELS))
     import numpy as np
-    import torch
-    from .fit_motion import read_gray_png
-    from .flo import read_flo
+    from ._cli import load_array, load_flow, load_mask_png, mask_like_flow, refusing, to_device
     from .histograms import HOF, ZERO, motion_descriptors, motion_histograms
     from .motion import fit_motion
-    try:
-        flow = read_flo(a.flow)
-        mask = read_gray_png(a.mask) if a.mask else None
-        ids = np.load(a.ids) if a.ids else None
-    except (OSError, ValueError, zlib.error) as e:
-        sys.stderr.write("motion_histograms: %s\n" % e)
+    with refusing("motion_histograms") as inputs:
+        flow = load_flow(a.flow)
+        h, w = flow.shape[:2]
+        mask = mask_like_flow(load_mask_png(a.mask), a.mask, h, w)
+        ids = mask_like_flow(load_array(a.ids), a.ids, h, w, "int32")
+    if inputs.refused:
         return 1
-    h, w = flow.shape[:2]
-    if mask is not None and mask.shape != (h, w):
-        sys.stderr.write("motion_histograms: %s is %d x %d, the flow %d x %d\n" % (a.mask, mask.shape[1], mask.shape[0], w, h))
-        return 1
-    if ids is not None and (ids.shape != (h, w) or ids.dtype != np.int32):
-        sys.stderr.write("motion_histograms: %s must hold an int32 array of %d x %d\n" % (a.ids, h, w))
-        return 1
-    dev = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    f, m = dev(flow), dev(mask)
+    f, m = to_device(flow), to_device(mask)
     params = None if a.model == "none" else fit_motion(f, m, a.model)
-    out = motion_histograms(f, m, params, a.cell, a.thresh, dev(ids), a.rows)
+    out = motion_histograms(f, m, params, a.cell, a.thresh, to_device(ids), a.rows)
     cells = out[0] if ids is not None else out
     save = {"cells": cells.cpu().numpy(), "descriptors": motion_descriptors(cells).cpu().numpy()}
     if ids is not None:

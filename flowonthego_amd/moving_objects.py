@@ -10,7 +10,6 @@ xmin ymin xmax ymax  area  centroid x y  mean motion u v (pixels, relative to th
 The module is callable: flowonthego_amd.moving_objects(flow, ...) is flowonthego_amd.objects.moving_objects(flow, ...)."""
 import argparse
 import sys
-import zlib
 
 from ._lib import callable_module
 
@@ -33,24 +32,16 @@ def main(argv=None):
     if a.min_area < 1 or a.max_objects < 1 or a.max_objects > 65536:
         ap.error("--min-area must be >= 1 and --max-objects in 1 .. 65536")
     import numpy as np
-    import torch
-    from .color import write_png
-    from .fit_motion import read_gray_png
-    from .flo import read_flo
+    from ._cli import load_flow, load_mask_png, mask_like_flow, refusing, save_code_png, to_device
     from .objects import moving_objects, object_summary
-    try:
-        flow = read_flo(a.flow)
-        mask = read_gray_png(a.mask) if a.mask else None
-    except (OSError, ValueError, zlib.error) as e:
-        sys.stderr.write("moving_objects: %s\n" % e)
+    with refusing("moving_objects") as inputs:
+        flow = load_flow(a.flow)
+        h, w = flow.shape[:2]
+        mask = mask_like_flow(load_mask_png(a.mask), a.mask, h, w)
+    if inputs.refused:
         return 1
-    h, w = flow.shape[:2]
-    if mask is not None and mask.shape != (h, w):
-        sys.stderr.write("moving_objects: %s is %d x %d, the flow %d x %d\n" % (a.mask, mask.shape[1], mask.shape[0], w, h))
-        return 1
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    params, objects, ids, st = moving_objects(dev(flow), None if mask is None else dev(mask), a.model, a.iters, a.thresh, a.min_area,
-                                              a.max_objects, a.connectivity, ids=True, stats=True)
+    params, objects, ids, st = moving_objects(to_device(flow), to_device(mask), a.model, a.iters, a.thresh, a.min_area, a.max_objects,
+                                              a.connectivity, ids=True, stats=True)
     st = st.cpu().numpy()
     print(" ".join("%.9g" % v for v in params.cpu().numpy()))
     rows = objects[:int(st[3])]
@@ -59,11 +50,10 @@ def main(argv=None):
     print("%d objects of at least %d pixels (%d components, %d pixels)%s" % (st[2], a.min_area, st[1], st[0],
                                                                              "" if st[2] == st[3] else ", the first %d listed" % st[3]))
     if a.ids:
-        k = ids.cpu().numpy().astype(np.int64) + 1
         pal = np.zeros((a.max_objects + 1, 3), np.uint8)
         j = np.arange(1, a.max_objects + 1)
         pal[1:] = np.stack([64 + (j * 97) % 192, 64 + (j * 57) % 192, 64 + (j * 151) % 192], -1)
-        write_png(a.ids, pal[k])
+        save_code_png(a.ids, ids + 1, pal)
     return 0
 
 

@@ -27,28 +27,13 @@ def main(argv=None):
     if a.radius < 0:
         ap.error("--radius must be >= 0")
     import numpy as np
-    import torch
-    from . import img_params, operating_point
-    from .oflow import OFClass
-    try:
-        frames = np.load(a.frames)
-    except (OSError, ValueError) as e:
-        sys.stderr.write("stabilize: %s\n" % e)
+    from ._cli import drop_c1, frame_sequence, refusing, sequence_context, to_device
+    with refusing("stabilize") as inputs:
+        frames = drop_c1(frame_sequence(a.frames, 2, "T+1", c1=True))
+    if inputs.refused:
         return 1
-    if frames.ndim not in (3, 4) or frames.shape[0] < 2 or frames.dtype not in (np.uint8, np.float32) or (frames.ndim == 4 and frames.shape[3] not in (1, 3)):
-        sys.stderr.write("stabilize: %s must hold a (T+1, h, w) or (T+1, h, w, 3) uint8 or float32 array, T >= 1\n" % a.frames)
-        return 1
-    if frames.ndim == 4 and frames.shape[3] == 1:
-        frames = frames[..., 0]
-    T, h, w = frames.shape[0] - 1, frames.shape[1], frames.shape[2]
-    color = frames.ndim == 4
-    u8_rgb = color and frames.dtype == np.uint8          # 8-bit colour frames become gray on load; float32 ones are used as RGB
-    op = operating_point(a.op_point, w, 3 if color and not u8_rgb else 1)
-    op.bidir = True
-    if u8_rgb:
-        op.u8_color = 2
-    ofc = OFClass(op, img_params(width=w, height=h), max_batch=T)
-    out, code = ofc.stabilize(torch.from_numpy(np.ascontiguousarray(frames)).cuda(), model=a.model, radius=a.radius, fill=a.fill)
+    ofc = sequence_context(frames, a.op_point, bidir=True, max_batch=frames.shape[0] - 1)
+    out, code = ofc.stabilize(to_device(frames), model=a.model, radius=a.radius, fill=a.fill)
     np.save(a.out, out.cpu().numpy())
     holes = (code != 0).float().mean(dim=(1, 2)).cpu().numpy()
     print("unfilled share per frame: " + " ".join("%.4f" % v for v in holes))

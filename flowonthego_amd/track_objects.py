@@ -41,31 +41,17 @@ def main(argv=None):
     if a.model not in MODELS:
         ap.error("--model must be one of " + ", ".join(MODELS))
     import numpy as np
-    import torch
-    from . import img_params, operating_point
-    from .oflow import OFClass
+    from ._cli import drop_c1, frame_sequence, refusing, sequence_context, to_device
     from .tracks import ENDS
-    try:
-        frames = np.load(a.frames)
-    except (OSError, ValueError) as e:
-        sys.stderr.write("track_objects: %s\n" % e)
+    with refusing("track_objects") as inputs:
+        frames = drop_c1(frame_sequence(a.frames, 3, "T+1", c1=True))
+    if inputs.refused:
         return 1
-    if frames.ndim not in (3, 4) or frames.shape[0] < 3 or frames.dtype not in (np.uint8, np.float32) or (frames.ndim == 4 and frames.shape[3] not in (1, 3)):
-        sys.stderr.write("track_objects: %s must hold a (T+1, h, w) or (T+1, h, w, 3) uint8 or float32 array, T >= 2\n" % a.frames)
-        return 1
-    if frames.ndim == 4 and frames.shape[3] == 1:
-        frames = frames[..., 0]
-    T, h, w = frames.shape[0] - 1, frames.shape[1], frames.shape[2]
-    color = frames.ndim == 4
-    u8_rgb = color and frames.dtype == np.uint8          # 8-bit colour frames become gray on load; float32 ones are used as RGB
-    op = operating_point(a.op_point, w, 3 if color and not u8_rgb else 1)
-    op.bidir = True
-    if u8_rgb:
-        op.u8_color = 2
-    ofc = OFClass(op, img_params(width=w, height=h), max_batch=T)
+    T = frames.shape[0] - 1
+    ofc = sequence_context(frames, a.op_point, bidir=True, max_batch=T)
     params, objects, track, tracks, ids, st = ofc.track_objects(
-        torch.from_numpy(np.ascontiguousarray(frames)).cuda(), model=a.model, iters=a.iters, thresh=a.thresh, min_area=a.min_area,
-        max_objects=a.max_objects, min_votes=a.min_votes, min_frac=a.min_frac, max_tracks=a.max_tracks, track_ids=True, stats=True)
+        to_device(frames), model=a.model, iters=a.iters, thresh=a.thresh, min_area=a.min_area, max_objects=a.max_objects,
+        min_votes=a.min_votes, min_frac=a.min_frac, max_tracks=a.max_tracks, track_ids=True, stats=True)
     st, table = st.cpu().numpy(), tracks.cpu().numpy()
     np.savez(a.out, params=params.cpu().numpy(), objects=objects.cpu().numpy(), track=track.cpu().numpy(), tracks=table, stats=st)
     if a.ids:

@@ -18,33 +18,22 @@ def main(argv=None):
     ap.add_argument("--occ", default=None)
     ap.add_argument("--fill", type=float, default=None)
     a = ap.parse_args(sys.argv[1:] if argv is None else argv)
-    import numpy as np
-    import torch
-    from .color import write_png
-    from .flo import read_flo
+    from ._cli import array_like_array, frame_like_flow, load_array, load_flow, mask_like_flow, refusing, save_frame_png, to_device
     from .warp import STATS, warp
-    try:
-        f0, f1, flow = np.load(a.f0), np.load(a.f1), read_flo(a.flow)
-        occ = np.load(a.occ) if a.occ else None
-    except (OSError, ValueError) as e:
-        sys.stderr.write("warp_frame: %s\n" % e)
+    with refusing("warp_frame") as inputs:
+        flow = load_flow(a.flow)
+        h, w = flow.shape[:2]
+        f0 = frame_like_flow(load_array(a.f0), a.f0, h, w)
+        f1 = array_like_array(frame_like_flow(load_array(a.f1), a.f1, h, w), a.f1, f0, a.f0)
+        occ = mask_like_flow(load_array(a.occ), a.occ, h, w)
+    if inputs.refused:
         return 1
-    h, w = flow.shape[:2]
-    if f0.shape != f1.shape or f0.dtype != f1.dtype or f0.dtype not in (np.uint8, np.float32) or f0.shape[:2] != (h, w) \
-            or f0.shape[2:] not in ((), (1,), (3,)) or (occ is not None and (occ.shape != (h, w) or occ.dtype != np.uint8)):
-        sys.stderr.write("warp_frame: the frames must be two alike (%d, %d[, 3]) uint8 or float32 arrays (the flow's size), "
-                         "the mask (%d, %d) uint8\n" % (h, w, h, w))
-        return 1
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    dst, _, st = warp(dev(f1), dev(flow), ref=dev(f0), occ=None if occ is None else dev(occ), fill=a.fill, stats=True)
+    dst, _, st = warp(to_device(f1), to_device(flow), ref=to_device(f0), occ=to_device(occ), fill=a.fill, stats=True)
     st = st.cpu().numpy()
     terms = max(st[0], 1.0) * (3 if f0.shape[2:] == (3,) else 1)
     print("  ".join("%s %.4f" % (nm, c / (h * w)) for nm, c in zip(STATS[:4], st[:4])) +
           "  mad_warped %.4f  mad_unwarped %.4f" % (st[4] / terms, st[5] / terms))
-    img = dst.cpu().numpy().reshape(h, w, -1)
-    if img.dtype != np.uint8:
-        img = np.clip(np.rint(np.nan_to_num(img)), 0, 255).astype(np.uint8)
-    write_png(a.out, np.ascontiguousarray(np.broadcast_to(img, (h, w, 3))))
+    save_frame_png(a.out, dst, h, w)
     return 0
 
 

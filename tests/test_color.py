@@ -3,13 +3,13 @@ code (tests/golden/colorcode_ref.npz, made by tests/golden/make_colorcode_golden
 the CLI's argument handling, the C-ABI declarations."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import colorcode_ref as R
 from conftest import ROOT
+from host_checks import run_cli
 
 
 def test_restatement_matches_reference_compute_color():
@@ -125,17 +125,14 @@ def test_color_flow_example_builds(tmp_path):
 
 
 def test_cli_argument_errors(tmp_path):
-    env = dict(os.environ, PYTHONPATH=ROOT)
     for args in ([], ["a.flo"], ["-quiet", "a.flo"], ["a.flo", "b.png", "3", "extra"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.color_flow"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
+        r = run_cli("color_flow", args)
         assert r.returncode != 0 and "usage: color_flow [-quiet] in.flo out.png [maxmotion]" in r.stderr, args
-    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.color_flow", "a.txt", "b.png"], capture_output=True, text=True, cwd=ROOT, env=env)
+    r = run_cli("color_flow", ["a.txt", "b.png"])
     assert r.returncode != 0 and "extension .flo expected" in r.stderr
-    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.color_flow", str(tmp_path / "none.flo"), "b.png"], capture_output=True,
-                       text=True, cwd=ROOT, env=env)
+    r = run_cli("color_flow", [str(tmp_path / "none.flo"), "b.png"])
     assert r.returncode != 0 and "ReadFlowFile" in r.stderr
-    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.color_flow", "a.flo", "b.png", "fast"], capture_output=True, text=True,
-                       cwd=ROOT, env=env)
+    r = run_cli("color_flow", ["a.flo", "b.png", "fast"])
     assert r.returncode != 0 and "maxmotion" in r.stderr
 
 

@@ -3,8 +3,6 @@ tests/test_gpu_histograms.py compares the kernel with the same restatement byte 
 import math
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,6 +10,7 @@ import pytest
 import histograms_ref as R
 
 from conftest import ROOT
+from host_checks import run_cli
 
 
 def one(U, V, thresh256=R.THRESH256):
@@ -179,9 +178,8 @@ def test_descriptors_against_numpy():
 
 
 def test_cli_argument_errors():
-    env = dict(os.environ, PYTHONPATH=ROOT)
     base = ["f.flo", "o.npz"]
     for args in ([], base[:1], base + ["extra"], base + ["--cell", "12"], base + ["--thresh", "-1"], base + ["--model", "rigid"],
                  base + ["--rows", "0"], base + ["--rows", "1025"], base + ["--mask"], base + ["--nosuch"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.motion_histograms"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
+        r = run_cli("motion_histograms", args)
         assert r.returncode != 0 and "usage" in r.stderr, args

@@ -104,6 +104,55 @@ def test_host_scaffold_exists_once():
     assert "(types.ModuleType)" in open(os.path.join(pkg, "_lib.py")).read()
 
 
+CLI_TOOLS = ("block_motion", "chain_flow", "denoise", "fb_check", "filter_flow", "fit_motion", "interp_frame", "motion_blur", "motion_histograms",
+             "moving_objects", "stabilize", "track_objects", "warp_frame")
+
+
+def test_cli_scaffold_exists_once():
+    """the file-and-device scaffold of the command-line tools lives in _cli.py and the PNG codec in _png.py: a new tool calls them
+    instead of pasting its own copy, and no tool imports from another tool"""
+    pkg = os.path.join(ROOT, "flowonthego_amd")
+    for tool in CLI_TOOLS:
+        txt = open(os.path.join(pkg, tool + ".py")).read()
+        for copied in ("torch.from_numpy", "dev = lambda", "except (OSError", "u8_color", "import zlib", "import struct"):
+            assert copied not in txt, (tool, copied)
+        assert "from ._cli import" in txt and "with refusing(\"%s\")" % tool in txt, tool
+        assert not re.search(r"from \.(%s) import" % "|".join(CLI_TOOLS), txt), tool
+    palette, defs = 0, {}
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            txt = open(os.path.join(pkg, f)).read()
+            palette += txt.count("(255, 255, 255), (220, 30, 30), (128, 128, 128), (0, 0, 0)")
+            for name in re.findall(r"def\s+(read_gray_png|write_png)\b", txt):
+                defs.setdefault(name, []).append(f)
+    assert palette == 1 and defs == {"write_png": ["_png.py"], "read_gray_png": ["_png.py"]}, (palette, defs)
+    import flowonthego_amd as F
+    from flowonthego_amd import _png, color, fit_motion
+    assert color.write_png is _png.write_png and F.write_png is _png.write_png and fit_motion.read_gray_png is _png.read_gray_png
+
+
+def test_every_lazy_name_is_the_object_its_module_defines():
+    """the package's table of lazy names: every name resolves to the attribute of its module, a function or class among them is
+    defined in that module, and the command-line modules come back as callable modules with a main()"""
+    import importlib
+    import types
+    import flowonthego_amd as F
+    assert not set(F.LAZY) & set(F.CLI_MODULES) and len(set(F.CLI_MODULES)) == len(F.CLI_MODULES)
+    for name, (module, attr) in F.LAZY.items():
+        m = importlib.import_module("flowonthego_amd." + module)
+        got = F.__getattr__(name)                       # (not getattr: importing a submodule binds its own name in the package)
+        assert got is getattr(m, attr), name
+        assert getattr(got, "__module__", m.__name__) == m.__name__, name
+        assert attr == name or name == "BLUR_STATS", name
+    assert F.LAZY["BLUR_STATS"] == ("motionblur", "STATS") and F.BLUR_STATS is importlib.import_module("flowonthego_amd.motionblur").STATS
+    for name in F.CLI_MODULES:
+        got = F.__getattr__(name)
+        assert isinstance(got, types.ModuleType) and got.__name__ == "flowonthego_amd." + name and callable(got) and callable(got.main), name
+        assert getattr(F, name) is got
+    with pytest.raises(AttributeError):
+        F.no_such_name
+
+
 def test_flo_writer_matches_reference_file_layout(tmp_path, alley_golden_flow):
     """write_flo == SaveFlowFile (kroeger/run_dense.cpp:16-57): tag, int32 w, int32 h, h*w*2 float32; the golden flow of the
     reference's own kroeger/flows/alley_0001.flo (tests/golden/alley_0001_flo.npz) survives a round trip bit for bit"""

@@ -3,14 +3,11 @@ against the C++ shim, the CLI refuses bad arguments, and the compiler's resource
 without a private-memory segment.  With a GPU: the CLI writes what block_motion returns and prints its numbers."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from host_checks import cli_refuses, entry_points, resource_table
+from host_checks import cli_refuses, entry_points, resource_table, run_cli
 
 NEW_SYMBOLS = ("fotg_block_motion", "fotg_upsample_crop_block_motion")
 
@@ -67,9 +64,8 @@ def test_cli_writes_what_the_call_returns(tmp_path):
     np.save(r, ref)
     write_flo(a, fw)
     write_flo(b, bw)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    run = subprocess.run([sys.executable, "-m", "flowonthego_amd.block_motion", c, r, a, o, "--block", "8", "--refine", "3", "--bw", b,
-                          "--pred", p], capture_output=True, text=True, cwd=ROOT, env=env)
+    run = run_cli("block_motion", [c, r, a, o, "--block", "8", "--refine", "3", "--bw", b,
+                          "--pred", p])
     assert run.returncode == 0, run.stderr
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
     mask = fb_check(dev(fw), dev(bw))[0]

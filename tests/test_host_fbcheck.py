@@ -1,17 +1,12 @@
 """The consistency check's tools: examples/fb_check.cpp compiles and links against the C++ shim (no GPU needed), and the
 python -m flowonthego_amd.fb_check CLI writes the mask PNG of the numpy restatement (GPU)."""
 import os
-import struct
-import subprocess
-import sys
-import zlib
 
 import numpy as np
 import pytest
 
 import fbcheck_ref as R
-from conftest import ROOT
-from host_checks import cli_refuses
+from host_checks import cli_refuses, read_png_rgb, run_cli
 
 
 def test_fb_check_example_builds(tmp_path):
@@ -25,24 +20,6 @@ def test_cli_argument_errors(tmp_path):
     cli_refuses("fb_check", ([], ["a.flo"], ["a.flo", "b.flo"], ["a.flo", "b.flo", "c.png", "--alpha1", "x"]))
 
 
-def read_png_rgb(path):
-    """the single-IDAT, filter-0 RGB PNGs color.write_png writes"""
-    data = open(path, "rb").read()
-    assert data[:8] == b"\x89PNG\r\n\x1a\n"
-    pos, idat, w, h = 8, b"", None, None
-    while pos < len(data):
-        n, = struct.unpack(">I", data[pos:pos + 4])
-        tag, body = data[pos + 4:pos + 8], data[pos + 8:pos + 8 + n]
-        if tag == b"IHDR":
-            w, h = struct.unpack(">II", body[:8])
-        elif tag == b"IDAT":
-            idat += body
-        pos += 12 + n
-    raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + 3 * w)
-    assert not raw[:, 0].any()
-    return raw[:, 1:].reshape(h, w, 3)
-
-
 @pytest.mark.gpu
 def test_cli_writes_the_mask_of_the_restatement(tmp_path):
     from flowonthego_amd.flo import write_flo
@@ -54,9 +31,7 @@ def test_cli_writes_the_mask_of_the_restatement(tmp_path):
     a, b, out = (str(tmp_path / n) for n in ("fw.flo", "bw.flo", "mask.png"))
     write_flo(a, fw)
     write_flo(b, bw)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.fb_check", a, b, out, "--alpha1", "0.02", "--alpha2", "0.4"],
-                       capture_output=True, text=True, cwd=ROOT, env=env)
+    r = run_cli("fb_check", [a, b, out, "--alpha1", "0.02", "--alpha2", "0.4"])
     assert r.returncode == 0, r.stderr
     want = R.fb_code(fw, bw, 0.02, 0.4)
     palette = np.array([(255, 255, 255), (255, 0, 0), (0, 0, 255), (0, 0, 0)], np.uint8)

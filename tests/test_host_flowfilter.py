@@ -3,14 +3,11 @@ the C++ shim, the CLI refuses bad arguments, and the compiler's resource table l
 private-memory segment.  With a GPU: the CLI writes what filter_flow returns and prints its numbers."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from host_checks import cli_refuses, entry_points, resource_table
+from host_checks import cli_refuses, entry_points, resource_table, run_cli
 
 NEW_SYMBOLS = ("fotg_flow_filter", "fotg_flow_filter_u8", "fotg_upsample_crop_flow_filter", "fotg_upsample_crop_flow_filter_u8")
 
@@ -76,9 +73,8 @@ def test_cli_writes_what_the_call_returns(tmp_path):
     write_flo(a, fw)
     write_flo(b, bw)
     np.save(g, guide)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.filter_flow", a, g, o, "--bw", b, "--radius", "4", "--sigma", "2",
-                        "--tau", "15", "--iters", "2", "--code", c], capture_output=True, text=True, cwd=ROOT, env=env)
+    r = run_cli("filter_flow", [a, g, o, "--bw", b, "--radius", "4", "--sigma", "2",
+                        "--tau", "15", "--iters", "2", "--code", c])
     assert r.returncode == 0, r.stderr
     dev = lambda x: torch.from_numpy(x).cuda()
     mask = fb_check(dev(fw), dev(bw))[0]

@@ -5,12 +5,11 @@ the CLI writes what the calls return."""
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import pytest
 
 from conftest import ROOT
-from host_checks import entry_points, resource_table
+from host_checks import entry_points, resource_table, run_cli
 
 NEW_SYMBOLS = ("fotg_motion_histograms", "fotg_upsample_crop_motion_histograms")
 FOTG_ERR_ARG = 1
@@ -96,9 +95,8 @@ def test_cli_writes_what_the_call_returns(tmp_path):
     fl, out, idf = (str(tmp_path / n) for n in ("f.flo", "out.npz", "ids.npy"))
     write_flo(fl, flow)
     np.save(idf, ids)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    run = subprocess.run([sys.executable, "-m", "flowonthego_amd.motion_histograms", fl, out, "--cell", "8", "--thresh", "0.5", "--model", "affine",
-                          "--ids", idf, "--rows", "3"], capture_output=True, text=True, cwd=ROOT, env=env)
+    run = run_cli("motion_histograms", [fl, out, "--cell", "8", "--thresh", "0.5", "--model", "affine",
+                          "--ids", idf, "--rows", "3"])
     assert run.returncode == 0, run.stderr
     dflow = torch.from_numpy(flow).cuda()
     params = F.fit_motion(dflow, None, "affine")

@@ -4,15 +4,12 @@ the compiler's resource table lists every interpolation kernel without a private
 restatement's frame."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import interp_ref as I
-from conftest import ROOT
-from host_checks import cli_refuses, entry_points, resource_table
+from host_checks import cli_refuses, entry_points, resource_table, run_cli
 
 NEW_SYMBOLS = ("fotg_interp", "fotg_interp_u8", "fotg_upsample_crop_interp", "fotg_upsample_crop_interp_u8")
 FOTG_ERR_ARG = 1
@@ -72,14 +69,12 @@ def test_resource_table_lists_the_interpolation_kernels_without_scratch():
 @pytest.mark.gpu
 def test_cli_writes_the_frame_of_the_restatement(tmp_path, alley):
     from oracle import oracle as O
-    from test_host_fbcheck import read_png_rgb
+    from host_checks import read_png_rgb
     f0, f1 = alley["frame_0001"][100:292, 300:620].copy(), alley["frame_0002"][100:292, 300:620].copy()
     a, b, out = (str(tmp_path / n) for n in ("f0.npy", "f1.npy", "out.png"))
     np.save(a, f0)
     np.save(b, f1)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.interp_frame", a, b, "0.25", out, "--ref", b],
-                       capture_output=True, text=True, cwd=ROOT, env=env)
+    r = run_cli("interp_frame", [a, b, "0.25", out, "--ref", b])
     assert r.returncode == 0, r.stderr
     g0, g1 = f0.astype(np.float32), f1.astype(np.float32)
     dst, code, st = I.interp(f0, f1, O.full_flow(g0, g1), O.full_flow(g1, g0), 0.25, ref=f1)

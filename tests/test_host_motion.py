@@ -1,13 +1,14 @@
 """The global-motion fit's host side (no GPU needed): the C-ABI is declared and bound, examples/fit_motion.cpp compiles and links
 against the C++ shim, the two command-line tools refuse bad arguments, and the compiler's resource table lists every instantiation
-of the motion kernels without a private-memory segment."""
+of the motion kernels without a private-memory segment.  With a GPU: the two tools write and print what the calls return."""
 import os
 import subprocess
 
 import numpy as np
+import pytest
 
 from conftest import ROOT
-from host_checks import cli_refuses, entry_points, resource_table
+from host_checks import cli_refuses, entry_points, gray_png_bytes, read_png_rgb, resource_table, run_cli
 
 NEW_SYMBOLS = ("fotg_fit_motion", "fotg_upsample_crop_fit_motion", "fotg_motion_flow", "fotg_motion_ending")
 
@@ -94,3 +95,67 @@ def test_resource_table_lists_the_motion_kernels_without_scratch():
         assert len(hit) == 1, w
         assert table[hit[0]] == 0, hit
     assert len([n for n in names if "motion_" in n]) == len(want)                  # and no instantiation beyond these
+
+
+@pytest.mark.gpu
+def test_fit_motion_cli_prints_and_writes_what_the_call_returns(tmp_path):
+    import torch
+    import flowonthego_amd as F
+    from flowonthego_amd.flo import write_flo
+    rng = np.random.default_rng(15)
+    h, w = 23, 41
+    ys, xs = np.mgrid[0:h, 0:w]
+    flow = (np.stack([0.02 * xs - 0.01 * ys + 1.5, 0.01 * xs + 0.03 * ys - 0.5], -1) + 0.2 * rng.standard_normal((h, w, 2))).astype(np.float32)
+    flow[5:11, 20:30] += 4.0                              # a patch that moves on its own
+    flow[3, 7] = (np.nan, 0)
+    mask = (rng.random((h, w)) < 0.1).astype(np.uint8) * 200
+    fl, mk, cd = (str(tmp_path / n) for n in ("f.flo", "m.png", "code.png"))
+    write_flo(fl, flow)
+    open(mk, "wb").write(gray_png_bytes(mask))
+    run = run_cli("fit_motion", [fl, "--mask", mk, "--model", "affine", "--code", cd])
+    assert run.returncode == 0, run.stderr
+    params, code, st = F.fit_motion(torch.from_numpy(flow).cuda(), torch.from_numpy(mask).cuda(), "affine", 3, 1.0, code=True, stats=True)
+    lines = run.stdout.splitlines()
+    assert len(lines) == 2 and lines[0] == " ".join("%.9g" % v for v in params.cpu().numpy())
+    code, st = code.cpu().numpy(), st.cpu().numpy()
+    assert len(set(code.ravel().tolist())) == 4           # follows, independent, masked and unknown all occur
+    assert lines[1] == "  ".join("%s %.4f" % (nm, c / (h * w)) for nm, c in zip(F.CODES, st[:4]))
+    palette = np.array([(255, 255, 255), (220, 30, 30), (128, 128, 128), (0, 0, 0)], np.uint8)
+    assert np.array_equal(read_png_rgb(cd), palette[code])
+
+
+def _stabilize_frames(form):
+    ys, xs = np.mgrid[0:48, 0:64]
+    rgb = np.stack([np.stack([128 + 60 * np.sin((ys + k + 3 * c) / 6.0) + 50 * np.cos((xs - 2 * k - c) / 5.0) for c in range(3)], -1)
+                    for k in range(4)])
+    rgb = np.clip(np.rint(rgb), 0, 255)
+    return {"gray": rgb[..., 0].astype(np.uint8), "gray_c1": rgb[..., :1].astype(np.uint8), "rgb_u8": rgb.astype(np.uint8),
+            "rgb_f32": rgb.astype(np.float32)}[form]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["gray", "gray_c1", "rgb_u8", "rgb_f32"])
+def test_stabilize_cli_writes_what_the_call_returns(tmp_path, form):
+    """the context as the tool's text describes it: both directions, one pair per frame step; 8-bit gray frames (with or without
+    a trailing channel of 1) on one channel, 8-bit colour made gray from R, G, B on load, float32 colour on three channels"""
+    import torch
+    import flowonthego_amd as F
+    from flowonthego_amd.oflow import OFClass
+    frames = _stabilize_frames(form)
+    a, b = str(tmp_path / "frames.npy"), str(tmp_path / "out.npy")
+    np.save(a, frames)
+    run = run_cli("stabilize", [a, b, "--radius", "2"])
+    assert run.returncode == 0, run.stderr
+    given = frames[..., 0] if form == "gray_c1" else frames
+    op = F.operating_point(2, 64, 3 if form == "rgb_f32" else 1)
+    op.bidir = True
+    if form == "rgb_u8":
+        op.u8_color = 2
+    ofc = OFClass(op, F.img_params(width=64, height=48), max_batch=3)
+    out, code = ofc.stabilize(torch.from_numpy(given).cuda(), model="similarity", radius=2, fill=None)
+    want = out.cpu().numpy()
+    holes = (code != 0).float().mean(dim=(1, 2)).cpu().numpy()
+    ofc.close()
+    got = np.load(b)
+    assert got.dtype == frames.dtype and got.shape == given.shape and got.tobytes() == want.tobytes()
+    assert run.stdout == "unfilled share per frame: " + " ".join("%.4f" % v for v in holes) + "\n"

@@ -5,12 +5,11 @@ writes what the call returns."""
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import pytest
 
 from conftest import ROOT
-from host_checks import cli_refuses, entry_points, resource_table
+from host_checks import cli_refuses, entry_points, resource_table, run_cli
 
 NEW_SYMBOLS = ("fotg_motion_blur", "fotg_upsample_crop_motion_blur")
 FOTG_ERR_ARG = 1
@@ -112,9 +111,7 @@ def test_cli_writes_what_the_call_returns(tmp_path):
     fr, fl, out, cd = (str(tmp_path / n) for n in ("f.npy", "f.flo", "out.png", "code.png"))
     np.save(fr, frame)
     write_flo(fl, flow)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    run = subprocess.run([sys.executable, "-m", "flowonthego_amd.motion_blur", fr, fl, out, "--shutter", "0.75", "--max-blur", "9", "--code", cd],
-                         capture_output=True, text=True, cwd=ROOT, env=env)
+    run = run_cli("motion_blur", [fr, fl, out, "--shutter", "0.75", "--max-blur", "9", "--code", cd])
     assert run.returncode == 0, run.stderr
     dst, code, st = F.motion_blur(torch.from_numpy(frame).cuda(), torch.from_numpy(flow).cuda(), None, 0.75, 9, code=True, stats=True)
     wd, wc, _, ws = R.blur(frame[None], flow[None], None, 192, 9)

@@ -3,14 +3,11 @@ against the C++ shim, the CLI refuses bad arguments, and the compiler's resource
 without a private-memory segment.  With a GPU: the CLI writes what OFClass.temporal_filter returns and prints its numbers."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from host_checks import cli_refuses, entry_points, resource_table
+from host_checks import cli_refuses, entry_points, resource_table, run_cli
 
 NEW_SYMBOLS = ("fotg_temporal_filter", "fotg_temporal_filter_u8", "fotg_upsample_crop_temporal_filter",
                "fotg_upsample_crop_temporal_filter_u8")
@@ -71,9 +68,7 @@ def test_cli_writes_what_the_call_returns(tmp_path):
     a, b, c = (str(tmp_path / n) for n in ("noisy.npy", "out.npy", "clean.npy"))
     np.save(a, noisy)
     np.save(c, clean)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.denoise", a, b, "--radius", "1", "--tau", "25", "--ref", c],
-                       capture_output=True, text=True, cwd=ROOT, env=env)
+    r = run_cli("denoise", [a, b, "--radius", "1", "--tau", "25", "--ref", c])
     assert r.returncode == 0, r.stderr
     o = OFClass(F.operating_point(2, 64, 1), F.img_params(width=64, height=48), max_batch=8)
     dst, used, st = o.temporal_filter(torch.from_numpy(noisy).cuda(), radius=1, tau=25.0, ref=torch.from_numpy(clean).cuda(), stats=True)

@@ -5,13 +5,10 @@ writes what OFClass.track_objects returns and prints a line per track."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
-from conftest import ROOT
-from host_checks import cli_refuses, entry_points, resource_table
+from host_checks import cli_refuses, entry_points, resource_table, run_cli
 
 NEW_SYMBOLS = ("fotg_object_overlap", "fotg_upsample_crop_object_overlap", "fotg_object_links", "fotg_object_tracks")
 FOTG_ERR_ARG = 1
@@ -97,9 +94,8 @@ def test_cli_writes_what_the_call_returns(tmp_path, natural_images):
     T, (h, w) = len(frames) - 1, frames.shape[1:]
     fr, out, ids = (str(tmp_path / n) for n in ("frames.npy", "out.npz", "ids.npy"))
     np.save(fr, frames)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    run = subprocess.run([sys.executable, "-m", "flowonthego_amd.track_objects", fr, out, "--min-area", "16", "--max-objects", "32",
-                          "--min-votes", "8", "--max-tracks", "64", "--ids", ids], capture_output=True, text=True, cwd=ROOT, env=env)
+    run = run_cli("track_objects", [fr, out, "--min-area", "16", "--max-objects", "32",
+                          "--min-votes", "8", "--max-tracks", "64", "--ids", ids])
     assert run.returncode == 0, run.stderr
     op = F.operating_point(2, w, 1)
     op.bidir = True

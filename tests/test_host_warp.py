@@ -2,15 +2,12 @@
 the C++ shim, the CLI refuses bad arguments, and the compiler's resource table lists every warp_kernel instantiation without a
 private-memory segment.  With a GPU: the CLI writes the restatement's frame and prints its numbers."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import warp_ref as W
-from conftest import ROOT
-from host_checks import cli_refuses, entry_points, resource_table
+from host_checks import cli_refuses, entry_points, resource_table, run_cli
 
 NEW_SYMBOLS = ("fotg_warp", "fotg_warp_u8", "fotg_upsample_crop_warp", "fotg_upsample_crop_warp_u8")
 
@@ -48,7 +45,7 @@ def test_resource_table_lists_the_warp_kernels_without_scratch():
 @pytest.mark.gpu
 def test_cli_writes_the_frame_of_the_restatement(tmp_path):
     from flowonthego_amd.flo import write_flo
-    from test_host_fbcheck import read_png_rgb
+    from host_checks import read_png_rgb
     rng = np.random.default_rng(4)
     h, w = 23, 41
     f0 = rng.integers(0, 256, (h, w)).astype(np.uint8)
@@ -61,9 +58,7 @@ def test_cli_writes_the_frame_of_the_restatement(tmp_path):
     np.save(b, f1)
     np.save(m, occ)
     write_flo(c, flow)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-m", "flowonthego_amd.warp_frame", a, b, c, out, "--occ", m, "--fill", "9"],
-                       capture_output=True, text=True, cwd=ROOT, env=env)
+    r = run_cli("warp_frame", [a, b, c, out, "--occ", m, "--fill", "9"])
     assert r.returncode == 0, r.stderr
     dst, code, st = W.warp(f1, flow, ref=f0, occ=occ, fill_mode=1, fill=9.0)
     assert np.array_equal(read_png_rgb(out), np.repeat(dst[..., None], 3, axis=2))

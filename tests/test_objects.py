@@ -6,13 +6,13 @@ import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import objects_ref as R
 from conftest import ROOT
+from host_checks import run_cli
 
 FOTG_ERR_ARG = 1
 
@@ -207,10 +207,9 @@ def test_moving_objects_example_builds(tmp_path):
 
 
 def test_cli_argument_errors():
-    env = dict(os.environ, PYTHONPATH=ROOT)
     for args in ([], ["a.flo", "b.flo"], ["a.flo", "--connectivity", "6"], ["a.flo", "--min-area", "0"], ["a.flo", "--max-objects", "70000"],
                  ["a.flo", "--model", "projective"], ["a.flo", "--ids"]):
-        r = subprocess.run([sys.executable, "-m", "flowonthego_amd.moving_objects"] + args, capture_output=True, text=True, cwd=ROOT, env=env)
+        r = run_cli("moving_objects", args)
         assert r.returncode != 0 and "usage" in r.stderr, args
 
 
