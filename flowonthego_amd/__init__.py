@@ -29,14 +29,15 @@ LAZY = {
     **_names("histograms", "upsample_crop_motion_histograms", "motion_descriptors", "HIST"),
     **_names("motionblur", "upsample_crop_motion_blur"),
     "BLUR_STATS": ("motionblur", "STATS"),
+    **_names("plate", "background_plate", "upsample_crop_background_plate", "plate_motions", "mosaic_canvas"),
     **_names("interp", "interpolate", "upsample_crop_interpolate"),
     **_names("pipeline", "FlowPipeline"),
     **_names("node", "FlowNode"),
 }
 
 # the command-line modules that are returned as modules: each is callable as the function of its name in flowonthego_amd.flowfilter /
-# blockmotion / motion / objects / tracks / histograms / motionblur
-CLI_MODULES = ["filter_flow", "block_motion", "fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms", "motion_blur"]
+# blockmotion / motion / objects / tracks / histograms / motionblur / plate
+CLI_MODULES = ["filter_flow", "block_motion", "fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms", "motion_blur", "background"]
 
 
 def __getattr__(name):

@@ -110,6 +110,13 @@ SYMBOLS = [
     ("fotg_upsample_crop_motion_histograms", C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
     ("fotg_motion_blur", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     ("fotg_upsample_crop_motion_blur", C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    ("fotg_plate", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_plate_u8", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_plate_motion", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_plate_motion_u8", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_plate", C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_upsample_crop_plate_u8", C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
+    ("fotg_plate_rows", C.c_int, [C.c_int]),
     ("fotg_level_size", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_out_size", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_num_patches", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

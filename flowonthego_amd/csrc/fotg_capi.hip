@@ -938,20 +938,11 @@ static VrPlan plan_level(const fotg_ctx *c, int l, int n)
   return p;
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: opt kernel fn in to lds bytes once per (kernel,
-// device).  Contexts / pipes driven from different host threads share the cache.
-static std::mutex g_lds_mu;
-static std::map<std::pair<const void *, int>, int> g_lds_set;
+// opt kernel fn in to lds bytes of dynamic LDS (host_call.h lds_opt_in), as a status
 template <typename... A>
 static int opt_in_lds(void (*fn)(A...), int lds)
 {
-  std::lock_guard<std::mutex> lock(g_lds_mu);
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  int &have = g_lds_set[{reinterpret_cast<const void *>(fn), dev}];
-  if (lds <= have) return FOTG_OK;
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  have = lds;
+  HIPCHK(lds_opt_in(fn, lds));
   return FOTG_OK;
 }
 

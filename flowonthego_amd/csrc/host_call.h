@@ -1,7 +1,11 @@
 // host_call.h -- the host-side scaffold every C-ABI file (fotg_<feature>.hip) shares: run on the context's device, report a HIP
 // failure, read a context's coarse flow in a fused entry point, refuse aliasing arguments (spans.h), own the stream-ordered memory
-// of one call.  An entry point decides FOTG_ERR_ARG first, from its arguments alone, and only then takes a DevGuard.
+// of one call, opt a kernel in to more dynamic LDS than the default limit.  An entry point decides FOTG_ERR_ARG first, from its
+// arguments alone, and only then takes a DevGuard.
 #pragma once
+#include <map>
+#include <mutex>
+#include <utility>
 #include "common.h"
 #include "flowsrc.hip.h"
 #include "spans.h"
@@ -70,6 +74,24 @@ struct Scratch {
     return e == hipSuccess ? FOTG_OK : hip_fail(e);
   }
 };
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: opt kernel fn in to lds bytes once per (kernel,
+// device), on the current device.  Contexts / pipes / calls driven from different host threads share the file's cache.
+std::mutex g_lds_mu;
+std::map<std::pair<const void *, int>, int> g_lds_set;
+template <typename... A>
+hipError_t lds_opt_in(void (*fn)(A...), int lds)
+{
+  std::lock_guard<std::mutex> lock(g_lds_mu);
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  int &have = g_lds_set[{reinterpret_cast<const void *>(fn), dev}];
+  if (lds <= have) return hipSuccess;
+  e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e == hipSuccess) have = lds;
+  return e;
+}
 
 }  // namespace
 }  // namespace fotg

@@ -365,6 +365,21 @@ class OFClass:
         from .motionblur import ofc_motion_blur
         return ofc_motion_blur(self, frames, shutter=shutter, max_blur=max_blur, occlusion=occlusion)
 
+    def upsample_crop_background_plate(self, flows, frames, index=None, occ=None, exclude=None, mode="median", min_count=1, fill=0,
+                                       ref=None, count=False, code=False, stats=False, fused=True):
+        """the median (or mean) over the frames pulled onto the frame grid along upsample_crop(flows), flows (n K, h_l, w_l, 2) of the
+        pairs (reference, frame); fused: the full-resolution flows are never written -- flowonthego_amd.plate"""
+        from .plate import upsample_crop_background_plate
+        return upsample_crop_background_plate(self, flows, frames, index=index, occ=occ, exclude=exclude, mode=mode, min_count=min_count,
+                                              fill=fill, ref=ref, count=count, code=code, stats=stats, fused=fused)
+
+    def background(self, frames, ref=0, model="affine", mosaic=False, mode="median", exclude_moving=True, min_count=1):
+        """frames (T+1, ...) -> (plate, code, count): the shot without its moving objects in the coordinates of frame ref, with mosaic
+        on the canvas that holds every frame -- flowonthego_amd.plate"""
+        from .plate import ofc_background
+        return ofc_background(self, frames, ref=ref, model=model, mosaic=mosaic, mode=mode, exclude_moving=exclude_moving,
+                              min_count=min_count)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

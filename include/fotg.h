@@ -829,6 +829,77 @@ int fotg_upsample_crop_motion_blur(fotg_ctx *ctx, int n, const void *src, int ty
                                    const unsigned char *mask, int shutter256, int max_blur, void *dst, unsigned char *code,
                                    short *vectors, long long *stats, void *stream);
 
+/* ---- background plates and mosaics: a median of frames along their motion, csrc/plate.hip.h -----------------------------------
+ * The frames of a shot are pulled into one coordinate system and reduced per pixel by a robust estimate over the frames that see
+ * the pixel: the clean plate (the scene without its moving objects), on a canvas larger than the frame the mosaic of a panning
+ * shot.  All arithmetic f32, every operation rounded on its own, in this order.
+ * Inputs: frames, a stack of T frames w x h x channels, channels 1 or 3 interleaved, f32 or 8-bit (the _u8 forms; taps converted
+ * exactly to f32), on the device, 1 <= w, h <= 16384.  n plates on a common W x H canvas, 1 <= W, H <= 16384, with an integer
+ * origin (ox, oy), |ox|, |oy| <= 2^20: canvas pixel (X, Y) is the reference coordinate (x, y) = (X - ox, Y - oy).  Per plate i K
+ * frame indices b_k = index[i K + k], 1 <= K <= 32, -1 = absent (skipped entirely).
+ * Vector per sample (i, k) at every canvas pixel, from one of three sources:
+ *   dense   fotg_plate:                flows n x K x H x W x 2 f32
+ *   motion  fotg_plate_motion:         params n x K x 6 f64 in fotg_fit_motion's pixel-frame convention for the w x h frame;
+ *           (u, v) = motion_predict(motion_coef(P, w, h), 2x - (w-1), 2y - (h-1)): fotg_motion_flow's arithmetic, evaluated at a
+ *           reference coordinate that may lie outside the frame
+ *   fused   fotg_upsample_crop_plate:  the coarse flows of a context, n K of them, upsampled and cropped on the fly; the canvas is
+ *           the frame grid (W = w_org, H = h_org, origin (0, 0)) and n K <= max_batch
+ * Admission: the samples are visited in ascending k; a sample is admitted by these tests, in this order:
+ *   1. u and v are finite
+ *   2. xx = (float)x + u and yy = (float)y + v satisfy fotg_warp's inside test (own == 0; otherwise own = 2)
+ *   3. occ is NULL or occ[i][k][Y][X] == 0                     (occ: n x K x H x W uint8 on the canvas grid)
+ *   4. exclude is NULL or it is zero at all four clamped tap pixels (x1|x2, y1|y2 of fotg_warp) of frame b_k
+ *                                                              (exclude: T x h x w uint8, per source frame)
+ *   5. no channel of the value s of fotg_warp's taps of frame b_k at (xx, yy) is NaN
+ * The number admitted is m, the number that passed tests 1 and 2 is the coverage.
+ * Estimate, per channel over the admitted values:
+ *   mode 0, the median: the values ordered by f32 <, ties keeping the k order; s[(m-1)/2] for odd m,
+ *           (s[m/2 - 1] + s[m/2]) * 0.5f for even m
+ *   mode 1, the mean:   sum = s_0; sum = sum + s_j for j = 1 .. m-1 in k order; sum / (float)m, a correctly rounded division
+ * Outputs, each may be NULL (not all of them), 1 <= min_count <= K:
+ *   dst    n x H x W x channels of the frames' type: the estimate where code == 0, `fill` elsewhere; an 8-bit dst (and fill) is
+ *          rounded as fotg_warp's
+ *   count  n x H x W uint8: m
+ *   code   n x H x W uint8: 0 where m >= min_count; 2 where fewer than min_count frames cover the pixel (coverage < min_count);
+ *          1 otherwise: the masks hid the covering frames
+ *   stats  n x 6 f64 per plate: [0..2] the pixels of code 0, 1, 2; [3] the sum of count; with a comparison image ref (n x H x W x
+ *          channels of dst's type) over the code-0 pixels and all channels [4] sum (double)|ref - estimate| and [5] sum
+ *          (double)|ref - s_0|, the first admitted sample: the overwrite mosaic as a baseline; each term the f32 fabsf of the f32
+ *          difference of the unrounded values; without ref both are 0.  The sums are added in a fixed order (no floating-point
+ *          atomics): the same bits every run, from every source and every launch shape.
+ * index is a HOST array: validated on the host and consumed before the call returns; it reaches the kernel by a stream-ordered
+ * copy into memory of the call.  Everything else is enqueued on `stream`; the partial sums live in stream-ordered memory of the call.
+ * FOTG_ERR_ARG, decided before the device is touched: n outside 1..65535, K outside 1..32, T < 1, a frame or canvas side outside
+ * 1..16384, an origin beyond 2^20, channels not 1 or 3, a mode other than 0 and 1, min_count outside 1..K, an index outside
+ * [-1, T), a null frames, source or index, all four outputs null, and by both rules of csrc/spans.h: an output (dst, count, code,
+ * stats) overlapping an input (frames, the source, occ, exclude, ref) -- overlap_any -- or another output -- overlap_among.  The
+ * fused forms also for a null or depth-mode context and n K > max_batch. */
+int fotg_plate(int device, int n, int K, int T, const float *frames, int w, int h, int channels, const int *index, const float *flows,
+               int W, int H, int ox, int oy, const unsigned char *occ, const unsigned char *exclude, int mode, int min_count, float fill,
+               const float *ref, float *dst, unsigned char *count, unsigned char *code, double *stats, void *stream);
+int fotg_plate_u8(int device, int n, int K, int T, const unsigned char *frames, int w, int h, int channels, const int *index,
+                  const float *flows, int W, int H, int ox, int oy, const unsigned char *occ, const unsigned char *exclude, int mode,
+                  int min_count, float fill, const unsigned char *ref, unsigned char *dst, unsigned char *count, unsigned char *code,
+                  double *stats, void *stream);
+int fotg_plate_motion(int device, int n, int K, int T, const float *frames, int w, int h, int channels, const int *index,
+                      const double *params, int W, int H, int ox, int oy, const unsigned char *occ, const unsigned char *exclude, int mode,
+                      int min_count, float fill, const float *ref, float *dst, unsigned char *count, unsigned char *code, double *stats,
+                      void *stream);
+int fotg_plate_motion_u8(int device, int n, int K, int T, const unsigned char *frames, int w, int h, int channels, const int *index,
+                         const double *params, int W, int H, int ox, int oy, const unsigned char *occ, const unsigned char *exclude,
+                         int mode, int min_count, float fill, const unsigned char *ref, unsigned char *dst, unsigned char *count,
+                         unsigned char *code, double *stats, void *stream);
+int fotg_upsample_crop_plate(fotg_ctx *ctx, int n, int K, int T, const float *coarse_flows, const float *frames, int channels,
+                             const int *index, const unsigned char *occ, const unsigned char *exclude, int mode, int min_count, float fill,
+                             const float *ref, float *dst, unsigned char *count, unsigned char *code, double *stats, void *stream);
+int fotg_upsample_crop_plate_u8(fotg_ctx *ctx, int n, int K, int T, const float *coarse_flows, const unsigned char *frames, int channels,
+                                const int *index, const unsigned char *occ, const unsigned char *exclude, int mode, int min_count,
+                                float fill, const unsigned char *ref, unsigned char *dst, unsigned char *count, unsigned char *code,
+                                double *stats, void *stream);
+/* Canvas rows per workgroup of the plate kernel (64 lanes each): 1, 2 or 4.  The results are the same bits; this exists to time
+ * the launch shapes.  Sets the process-wide value for later calls (any other value only queries) and returns the previous one. */
+int fotg_plate_rows(int rows);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
