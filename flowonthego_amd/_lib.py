@@ -108,6 +108,8 @@ SYMBOLS = [
     ("fotg_object_tracks", C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
     ("fotg_motion_histograms", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
     ("fotg_upsample_crop_motion_histograms", C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
+    ("fotg_motion_layers", C.c_int, [C.c_int, C.c_int, vp, vp] + [C.c_int] * 6 + [C.c_float] + [vp] * 8),
+    ("fotg_upsample_crop_motion_layers", C.c_int, [vp, C.c_int, vp, vp] + [C.c_int] * 4 + [C.c_float] + [vp] * 8),
     ("fotg_motion_blur", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     ("fotg_upsample_crop_motion_blur", C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     ("fotg_plate", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),

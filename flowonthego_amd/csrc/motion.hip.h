@@ -123,14 +123,34 @@ __device__ __forceinline__ void motion_dpp_stage(long long (&s)[K])
   for (int k = 0; k < K; ++k) s[k] += t[k];
 }
 
-// the workgroup's K sums: per wave by lane crossings of the two halves, per workgroup through LDS; thread k < K then stores sum k
-// to part[k] (part != null) or adds it to acc[k] with one 64-bit integer atomic.  Every thread of the workgroup calls it.
-template <int K>
-__device__ __forceinline__ void motion_block_reduce(long long (&s)[K], long long *__restrict__ acc, long long *__restrict__ part)
+// a selected pixel joins the twelve sums of the head of this file
+__device__ __forceinline__ void motion_add12(long long (&s)[12], int X, int Y, float u, float v)
 {
-  // stage by stage, the K sums of a stage side by side: their lane crossings are independent and in flight together.  Within a
-  // row of 16 lanes the crossings are DPP moves (lane ^ 1, lane ^ 2, then the mirrors of 8 and of 16 lanes: every lane of a row
-  // ends with the row's sum); across rows, xor shuffles by 16 and 32.
+  const long long U = (int)rintf(u * 256.f), V = (int)rintf(v * 256.f);
+  const long long Xl = X, Yl = Y;
+  s[0] += 1;       s[1] += Xl;      s[2] += Yl;
+  s[3] += Xl * Xl; s[4] += Xl * Yl; s[5] += Yl * Yl;
+  s[6] += U;       s[7] += Xl * U;  s[8] += Yl * U;
+  s[9] += V;       s[10] += Xl * V; s[11] += Yl * V;
+}
+
+// the mask bytes of a thread's nb (<= 4) pixels at o, byte i in bits 8i .. 8i+7: one 4-byte load where the address allows
+__device__ __forceinline__ unsigned motion_mask4(const unsigned char *__restrict__ o, int nb)
+{
+  if (nb == 4 && (((size_t)o) & 3) == 0) return *reinterpret_cast<const unsigned *>(o);
+  unsigned maskw = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < nb) maskw |= (unsigned)o[i] << (8 * i);
+  return maskw;
+}
+
+// the wave's K sums in every lane, stage by stage, the K sums of a stage side by side: their lane crossings are independent and
+// in flight together.  Within a row of 16 lanes the crossings are DPP moves (lane ^ 1, lane ^ 2, then the mirrors of 8 and of 16
+// lanes: every lane of a row ends with the row's sum); across rows, xor shuffles by 16 and 32.  All lanes of the wave active.
+template <int K>
+__device__ __forceinline__ void motion_wave_reduce(long long (&s)[K])
+{
   motion_dpp_stage<0xB1>(s);      // quad_perm [1 0 3 2]
   motion_dpp_stage<0x4E>(s);      // quad_perm [2 3 0 1]
   motion_dpp_stage<0x141>(s);     // row_half_mirror
@@ -147,6 +167,14 @@ __device__ __forceinline__ void motion_block_reduce(long long (&s)[K], long long
 #pragma unroll
     for (int k = 0; k < K; ++k) s[k] += t[k];
   }
+}
+
+// the workgroup's K sums: per wave by lane crossings of the two halves, per workgroup through LDS; thread k < K then stores sum k
+// to part[k] (part != null) or adds it to acc[k] with one 64-bit integer atomic.  Every thread of the workgroup calls it.
+template <int K>
+__device__ __forceinline__ void motion_block_reduce(long long (&s)[K], long long *__restrict__ acc, long long *__restrict__ part)
+{
+  motion_wave_reduce<K>(s);
   __shared__ long long ws[MOTION_THREADS / FOTG_WAVE][K];
   const int wave = threadIdx.x / FOTG_WAVE, lane = threadIdx.x % FOTG_WAVE;
   if (lane == 0) {
@@ -186,17 +214,7 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_pass_kernel(Src flow, c
     int y = (int)(r0 / w), x = (int)(r0 - (long)y * w);
     float u[4], v[4];
     warp_flow4(flow, base + r0, nb, pair, x, y, w, u, v);
-    unsigned maskw = 0;
-    if (mask) {
-      const unsigned char *o = mask + (size_t)base + (size_t)r0;
-      if (nb == 4 && (((size_t)o) & 3) == 0) {
-        maskw = *reinterpret_cast<const unsigned *>(o);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (i < nb) maskw |= (unsigned)o[i] << (8 * i);
-      }
-    }
+    const unsigned maskw = mask ? motion_mask4(mask + (size_t)base + (size_t)r0, nb) : 0u;
     float res[8];
     unsigned word = 0;
 #pragma unroll
@@ -217,14 +235,7 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_pass_kernel(Src flow, c
           word |= cd << (8 * i);
           s[0] += cd == 0; s[1] += cd == 1; s[2] += cd == 2; s[3] += cd == 3;
         } else {
-          if (cd == 0) {
-            const long long U = (int)rintf(u[i] * 256.f), V = (int)rintf(v[i] * 256.f);
-            const long long Xl = X, Yl = Y;
-            s[0] += 1;       s[1] += Xl;      s[2] += Yl;
-            s[3] += Xl * Xl; s[4] += Xl * Yl; s[5] += Yl * Yl;
-            s[6] += U;       s[7] += Xl * U;  s[8] += Yl * U;
-            s[9] += V;       s[10] += Xl * V; s[11] += Yl * V;
-          }
+          if (cd == 0) motion_add12(s, X, Y, u[i], v[i]);
         }
       }
       if (++x == w) { x = 0; ++y; }
@@ -254,6 +265,7 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_fold_kernel(const long 
   motion_block_reduce<K>(s, nullptr, out + (size_t)blockIdx.x * out_stride);
 }
 
+#ifndef FOTG_MOTION_NO_PLAIN_KERNELS     // (layers.hip.h shares the templates and helpers above; these two are compiled once, by fotg_motion.hip)
 // one thread per image: reads and clears the twelve accumulators, solves, writes the parameters (or keeps them and sets bad[i]).
 // sums_out (n x 12) and stats (n x 6: [4] the pixels in this fit, [5] fitted) are written where given -- the last round's.
 __global__ void motion_solve_kernel(long long *__restrict__ acc, int n, int model, int w, int h, double *__restrict__ params,
@@ -300,5 +312,7 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_flow_kernel(const doubl
   }
   warp_store4<float, 2>(flow + 2 * (size_t)(base + r0), val, nb);
 }
+
+#endif
 
 }  // namespace fotg

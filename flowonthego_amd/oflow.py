@@ -266,6 +266,22 @@ class OFClass:
         from .motion import ofc_stabilize
         return ofc_stabilize(self, frames, model=model, radius=radius, fill=fill, stats=stats, iters=iters, thresh=thresh)
 
+    def upsample_crop_motion_layers(self, coarse, mask=None, layers=3, model="affine", iters=3, rounds=3, thresh=1.0, init=None,
+                                    labels=False, residual=False, records=False, stats=False, sums=False, fused=False):
+        """up to `layers` motions fitted to upsample_crop(coarse), every pixel given to the nearest: params (n, K, 6) and what was
+        asked for -- flowonthego_amd.layers"""
+        from .layers import upsample_crop_motion_layers
+        return upsample_crop_motion_layers(self, coarse, mask, layers=layers, model=model, iters=iters, rounds=rounds, thresh=thresh,
+                                           init=init, labels=labels, residual=residual, records=records, stats=stats, sums=sums, fused=fused)
+
+    def motion_layers(self, frames, layers=3, model="affine", iters=3, rounds=3, thresh=1.0, labels=False, residual=False, records=False,
+                      stats=False, sums=False, fused=False):
+        """the flows of frames (T+1, ...) and the motion layers of each: params (T, K, 6) and what was asked for, occluded pixels
+        left out on a bidir context -- flowonthego_amd.layers"""
+        from .layers import ofc_motion_layers
+        return ofc_motion_layers(self, frames, layers=layers, model=model, iters=iters, rounds=rounds, thresh=thresh, labels=labels,
+                                 residual=residual, records=records, stats=stats, sums=sums, fused=fused)
+
     def moving_objects(self, frames, model="affine", iters=3, thresh=1.0, min_area=64, max_objects=256, connectivity=8, ids=False,
                        stats=False):
         """the flows of frames (T+1, ...), the camera motion of each, and the pixels that do not follow it grouped into objects:

@@ -508,6 +508,52 @@ int fotg_motion_flow(int device, int n, const double *params, int w, int h, floa
  * calls (any other value only queries) and returns the previous one. */
 int fotg_motion_ending(int ending);
 
+/* ---- motion layers: several parametric motions fitted to one flow, every pixel given to the nearest, csrc/layers.hip.h ----------
+ * The layered decomposition of Wang and Adelson on the pieces of the global-motion fit above: up to eight motions of one `model`,
+ * layer 0 the camera motion fotg_fit_motion finds, each further layer grown from the 32 x 32 tile that the earlier layers explain
+ * least, then all of them refined together.  layers: K in 1 .. 8; iters 0 .. 64; rounds 0 .. 64; thresh >= 0; init: NULL or
+ * n x K x 6 f64.  In order:
+ * Per pixel: X, Y, known, U, V and admissible as above.  For a layer with parameters P: (du, dv) = (u, v) - the prediction of P,
+ * r(P) = du du + dv dv, within(P) = r(P) <= thresh thresh (f32, every operation rounded on its own, thresh thresh one product).
+ * Every layer starts with zero parameters, live = fitted = 0, seed -1, zero sums.
+ * Seeding, k = 0 .. K-1 (skipped with init: every layer is then live and fitted with the caller's parameters, seed -2):
+ *   candidates = the admissible pixels within() no live layer j < k (a dead layer removes nothing).
+ *   k = 0: no seed tile (seed stays -1); rounds r = 0 .. iters select the candidates (r = 0) or the candidates within the layer's
+ *          parameters (r > 0), reduce the twelve sums and solve with `model`: params[0] equals fotg_fit_motion's byte for byte.
+ *   k >= 1: the candidates are counted per tile of 32 x 32 pixels (edge tiles partial, tile index = tile row x tiles per row +
+ *          tile column).  The seed tile has the most, the lowest index among equals; with no candidate the layer is dead (zeros,
+ *          seed -1).  Its first parameters are the translation solve of the seed tile's n, sum U, sum V; then iters + 1 rounds,
+ *          each over the candidates within the layer's current parameters, solved with `model`.
+ *   An unusable system keeps the previous parameters and clears `fitted`; the later rounds still run.  After the last round
+ *   live = fitted (a layer one of whose rounds was unusable is dead; its parameters stay as they are).
+ * Refinement, `rounds` times: assign every pixel -- best = none, rb = +infinity, db = (u, v); for the live layers j ascending:
+ *   less = r_j < rb; if best is none or less: best = j, db = (du_j, dv_j); if less: rb = r_j (ties go to the lower index, a NaN
+ *   never displaces a value); joined = admissible, best a layer, db.u db.u + db.v db.v <= thresh thresh.  Every live layer's twelve
+ *   sums run over the pixels joined to it and it is solved with `model`; an unusable system keeps its parameters and clears
+ *   `fitted`, the layer stays live.
+ * Final pass (skipped when none of its outputs is asked for): assign as above.  Outputs on the device, each but params may be NULL:
+ *   params   n x K x 6 f64  [a00 a01 tx a10 a11 ty] per layer, in fotg_fit_motion's convention; layers are not reordered
+ *   labels   n x h x w uint8: the layer where joined; 253 admissible but joined to none (or no layer live); 254 excluded by the
+ *            mask; 255 unknown (unknown wins over masked)
+ *   residual n x h x w x 2 f32: db, the flow minus the assigned layer's motion (the flow itself when no layer is live)
+ *   records  n x K x 8 int64: pixels labelled, pixels in the last fit, live, fitted, seed tile (-1 none, -2 init), sum X, sum Y,
+ *            sum U over the labelled pixels
+ *   stats    n x 4 int64: pixels of label 253, 254, 255, the number of live layers
+ *   sums     n x K x 12 int64: the sums of each layer's last fit (zeros for a layer that never had one)
+ * Integer sums are the same bits whatever the order and nothing is accumulated in floating point, so every output has one value
+ * per input.  Asynchronous on `stream`; the parameters never leave the device between passes.  FOTG_ERR_ARG: n < 1 (or > 65535),
+ * w or h < 1 or > 16384, layers outside 1 .. 8, a model, iters, rounds or thresh out of range (a NaN thresh too), a null flow or
+ * params, an output overlapping an input (init among them) or another output. */
+int fotg_motion_layers(int device, int n, const float *flow, const unsigned char *mask, int w, int h, int layers, int model, int iters,
+                       int rounds, float thresh, const double *init, double *params, unsigned char *labels, float *residual,
+                       long long *records, long long *stats, long long *sums, void *stream);
+/* The same on the coarse flow of a context (n x hl x wl x 2), upsampled and cropped on the fly in every pass; mask at the original
+ * size.  Every output equals the dense form on fotg_upsample_crop's output byte for byte.  FOTG_ERR_ARG also for n > max_batch and
+ * a depth-mode context. */
+int fotg_upsample_crop_motion_layers(fotg_ctx *ctx, int n, const float *coarse_flow, const unsigned char *mask, int layers, int model,
+                                     int iters, int rounds, float thresh, const double *init, double *params, unsigned char *labels,
+                                     float *residual, long long *records, long long *stats, long long *sums, void *stream);
+
 /* ---- objects: the connected components of a code map, with a record each, csrc/components.hip.h ---------------------------------
  * What turns the per-pixel codes of the motion fit (1 = independent motion), the consistency check or the warp into a list of
  * regions.  In order:
