@@ -396,6 +396,23 @@ class OFClass:
         return ofc_background(self, frames, ref=ref, model=model, mosaic=mosaic, mode=mode, exclude_moving=exclude_moving,
                               min_count=min_count)
 
+    def upsample_crop_subtract_background(self, flows, frames, plate, index=None, origin=(0, 0), plate_code=None, mask=None, low=8.0,
+                                          high=24.0, window=1, code=True, diff=False, evidence=False, stats=False, fused=True):
+        """every frame against the plate sampled along upsample_crop(flows), flows (n, h_l, w_l, 2) of the pairs (frame, reference);
+        fused: the full-resolution flows are never written -- flowonthego_amd.subtract"""
+        from .subtract import upsample_crop_subtract_background
+        return upsample_crop_subtract_background(self, flows, frames, plate, index=index, origin=origin, plate_code=plate_code, mask=mask,
+                                                 low=low, high=high, window=window, code=code, diff=diff, evidence=evidence, stats=stats,
+                                                 fused=fused)
+
+    def foreground(self, frames, ref=0, model="affine", low=8.0, high=24.0, window=1, min_area=64, max_objects=256, mode="median",
+                   exclude_moving=True):
+        """frames (T+1, ...) -> (mask, objects, confirmed, plate, code): the plate of the shot on frame ref's grid, every frame
+        subtracted from it, and the components that hold a strong pixel -- flowonthego_amd.subtract"""
+        from .subtract import ofc_foreground
+        return ofc_foreground(self, frames, ref=ref, model=model, low=low, high=high, window=window, min_area=min_area,
+                              max_objects=max_objects, mode=mode, exclude_moving=exclude_moving)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

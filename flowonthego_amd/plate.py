@@ -200,12 +200,9 @@ def mosaic_canvas(motions, w, h):
     return W, H, -x0, -y0
 
 
-def ofc_background(ofc, frames, ref=0, model="affine", mosaic=False, mode="median", exclude_moving=True, min_count=1):
-    """OFClass.background: frames (T+1, h, w[, c]), 2 <= T+1 <= 32 -> (plate, code, count) of the shot in the coordinates of frame
-    `ref`.  The composition, call for call: the sequence flows (on a bidir context with the forward consistency mask),
-    upsample_crop_fit_motion with its code, the code-1 pixels (independent motion) of frame k as exclude[k] (exclude_moving; a zero
-    map for the last frame, which has no flow), plate_motions(params, ref), the canvas -- the frame grid, or with mosaic
-    mosaic_canvas(motions, w, h) -- and background_plate(frames, None, motions=motions, ...) with code and count."""
+def _ofc_plate(ofc, frames, ref, model, mosaic, mode, exclude_moving, min_count):
+    """ofc_background's work: (plate, code, count, motions), motions (T+1, 6) the maps reference -> frame the plate was made with
+    (flowonthego_amd.subtract.ofc_foreground inverts them)"""
     from .motion import _sequence_flows, upsample_crop_fit_motion
     two_channel(ofc, "the background plate needs a two-channel flow")
     T1, h, w, ch, dtype = _frames(frames, ofc.device)
@@ -223,7 +220,16 @@ def ofc_background(ofc, frames, ref=0, model="affine", mosaic=False, mode="media
     W, H, ox, oy = mosaic_canvas(motions, w, h) if mosaic else (w, h, 0, 0)
     dst, cnt, code = background_plate(frames, None, motions=motions, canvas=(W, H), origin=(ox, oy), exclude=exclude, mode=mode,
                                       min_count=min_count, count=True, code=True)
-    return dst[0], code[0], cnt[0]
+    return dst[0], code[0], cnt[0], motions
+
+
+def ofc_background(ofc, frames, ref=0, model="affine", mosaic=False, mode="median", exclude_moving=True, min_count=1):
+    """OFClass.background: frames (T+1, h, w[, c]), 2 <= T+1 <= 32 -> (plate, code, count) of the shot in the coordinates of frame
+    `ref`.  The composition, call for call: the sequence flows (on a bidir context with the forward consistency mask),
+    upsample_crop_fit_motion with its code, the code-1 pixels (independent motion) of frame k as exclude[k] (exclude_moving; a zero
+    map for the last frame, which has no flow), plate_motions(params, ref), the canvas -- the frame grid, or with mosaic
+    mosaic_canvas(motions, w, h) -- and background_plate(frames, None, motions=motions, ...) with code and count."""
+    return _ofc_plate(ofc, frames, ref, model, mosaic, mode, exclude_moving, min_count)[:3]
 
 
 callable_module(__name__, __name__, "background_plate")

@@ -946,6 +946,76 @@ int fotg_upsample_crop_plate_u8(fotg_ctx *ctx, int n, int K, int T, const float 
  * the launch shapes.  Sets the process-wide value for later calls (any other value only queries) and returns the previous one. */
 int fotg_plate_rows(int rows);
 
+/* ---- background subtraction against a plate, with two thresholds for hysteresis, csrc/subtract.hip.h ---------------------------
+ * Every frame is compared with the plate (fotg_plate's output) sampled into the frame's own grid; the difference is averaged over
+ * a small window and classified by a low and a high threshold.  It finds what fotg_fit_motion's code cannot: an object that
+ * stops, one that moves slowly, the untextured inside of a large one.
+ * Inputs: n frames w x h x channels, channels 1 or 3 interleaved, f32 or 8-bit (the _u8 forms), 1 <= w, h <= 16384.  P plates of
+ * the frames' type and channel count on a W x H canvas, 1 <= W, H <= 16384, with an integer origin (ox, oy), |ox|, |oy| <= 2^20:
+ * canvas pixel (X, Y) is the reference coordinate (X - ox, Y - oy), as in fotg_plate.  index[i] in 0 .. P-1 is the plate of
+ * frame i, a HOST array of n entries; NULL: plate 0 for P == 1, plate i for P == n.
+ * The vector frame i -> reference at every frame pixel (x, y), from one of three sources:
+ *   dense   fotg_subtract:                flows n x h x w x 2 f32
+ *   motion  fotg_subtract_motion:         params n x 6 f64 in fotg_fit_motion's pixel-frame convention for the w x h frame;
+ *           (u, v) = motion_predict(motion_coef(P_i, w, h), 2x - (w-1), 2y - (h-1)): fotg_motion_flow's arithmetic
+ *   fused   fotg_upsample_crop_subtract:  the coarse flows of a context, n <= max_batch of them (the pairs (frame i, reference)),
+ *           upsampled and cropped on the fly; the frames have the context's original size; a two-channel context
+ * Per frame pixel, all arithmetic f32, every operation rounded on its own, in this order:
+ *   1. (u, v) not finite, or mask[i][y][x] != 0 (mask: n x h x w uint8 or NULL, fotg_fb_check's):           code 3
+ *   2. Xc = (float)(x + ox) + u;  Yc = (float)(y + oy) + v;  fotg_warp's inside test warp_inside(Xc, Yc, W, H) fails:   code 2
+ *   3. plate_code (P x H x W uint8 or NULL, fotg_plate's code) of plate index[i] is non-zero at any of the four clamped tap
+ *      pixels (x1|x2, y1|y2 of fotg_warp) at (Xc, Yc) -- the test of fotg_plate's exclude:                  code 2
+ *   4. s = fotg_warp's taps warp_taps(plate[index[i]], W, H, Xc, Yc); any channel of s or of the frame pixel f is NaN:  code 3
+ *   5. otherwise the pixel is admissible:
+ *        d  = 0;  per channel in order: e = fabsf(f_ch - s_ch);  d = e > d ? e : d    (the largest channel difference; the frame
+ *             value converted to float, the taps of an 8-bit plate left unrounded)
+ *        Dq = (int)(fminf(d * 16.f, 32767.f) + 0.5f)           the difference in 1/16 grey levels, saturating at 2047.9 levels
+ * Window: r = window in {0, 1, 2} (1 x 1, 3 x 3, 5 x 5); over the pixels of the frame within the window S = the sum of Dq over
+ * the admissible pixels and C = their number.  Everything after Dq is integer: no summation order matters.
+ * Thresholds: L = lrintf(16 low), Hh = lrintf(16 high), 0 <= L <= Hh <= 32767.
+ * Code of an admissible pixel: 4 (strong foreground) if S >= Hh * C, otherwise 1 (foreground) if S >= L * C, otherwise 0.
+ * Alphabet: 0 background, 1 foreground, 2 no plate there, 3 unknown, 4 strong foreground; 0 .. 3 mean what they mean in the other
+ * code maps, and fotg_label_components with the foreground set {1, 4} takes the map as it is.
+ * Outputs, each may be NULL (not all of them):
+ *   code      n x h x w uint8
+ *   diff      n x h x w int16: Dq at admissible pixels, 0 elsewhere
+ *   evidence  n x h x w x 2 f32: (code == 4 ? 1 : 0, Dq / 16), (0, 0) where inadmissible.  As the values of
+ *             fotg_label_components it makes a row's sum_u / 256 the number of strong pixels of the component -- a component
+ *             counts only if it holds one: the hysteresis -- and sum_v 16 times the sum of Dq, exactly
+ *   stats     n x 7 int64 per frame: [0..4] the pixels of code 0 .. 4, [5] the sum of Dq over the admissible pixels, [6] the sum of
+ *             Dq over the pixels of code 1 or 4.  Cleared by a stream-ordered memset inside the call and accumulated by integer
+ *             atomics: the same value every run.
+ * Everything is enqueued on `stream`; index is validated on the host and consumed before the call returns.
+ * FOTG_ERR_ARG, decided before the device is touched: n or P outside 1..65535, a frame or canvas side outside 1..16384, an origin
+ * beyond 2^20, channels not 1 or 3, a window outside 0..2, thresholds that are not finite or not 0 <= L <= Hh <= 32767, a plate
+ * index outside 0 .. P-1 (a NULL index with P other than 1 and n), a null frames, plate or source, all four outputs null, and by
+ * both rules of csrc/spans.h: an output (code, diff, evidence, stats) overlapping an input (frames, plate, the source,
+ * plate_code, mask) -- overlap_any -- or another output -- overlap_among.  The fused forms also for a null or depth-mode context
+ * and n > max_batch. */
+int fotg_subtract(int device, int n, const float *frames, int w, int h, int channels, int P, const float *plate, int W, int H, int ox,
+                  int oy, const int *index, const float *flows, const unsigned char *plate_code, const unsigned char *mask, float low,
+                  float high, int window, unsigned char *code, short *diff, float *evidence, long long *stats, void *stream);
+int fotg_subtract_u8(int device, int n, const unsigned char *frames, int w, int h, int channels, int P, const unsigned char *plate, int W,
+                     int H, int ox, int oy, const int *index, const float *flows, const unsigned char *plate_code,
+                     const unsigned char *mask, float low, float high, int window, unsigned char *code, short *diff, float *evidence,
+                     long long *stats, void *stream);
+int fotg_subtract_motion(int device, int n, const float *frames, int w, int h, int channels, int P, const float *plate, int W, int H,
+                         int ox, int oy, const int *index, const double *params, const unsigned char *plate_code,
+                         const unsigned char *mask, float low, float high, int window, unsigned char *code, short *diff, float *evidence,
+                         long long *stats, void *stream);
+int fotg_subtract_motion_u8(int device, int n, const unsigned char *frames, int w, int h, int channels, int P, const unsigned char *plate,
+                            int W, int H, int ox, int oy, const int *index, const double *params, const unsigned char *plate_code,
+                            const unsigned char *mask, float low, float high, int window, unsigned char *code, short *diff,
+                            float *evidence, long long *stats, void *stream);
+int fotg_upsample_crop_subtract(fotg_ctx *ctx, int n, const float *coarse_flows, const float *frames, int channels, int P,
+                                const float *plate, int W, int H, int ox, int oy, const int *index, const unsigned char *plate_code,
+                                const unsigned char *mask, float low, float high, int window, unsigned char *code, short *diff,
+                                float *evidence, long long *stats, void *stream);
+int fotg_upsample_crop_subtract_u8(fotg_ctx *ctx, int n, const float *coarse_flows, const unsigned char *frames, int channels, int P,
+                                   const unsigned char *plate, int W, int H, int ox, int oy, const int *index,
+                                   const unsigned char *plate_code, const unsigned char *mask, float low, float high, int window,
+                                   unsigned char *code, short *diff, float *evidence, long long *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
