@@ -32,14 +32,15 @@ LAZY = {
     **_names("plate", "background_plate", "upsample_crop_background_plate", "plate_motions", "mosaic_canvas"),
     **_names("layers", "upsample_crop_motion_layers", "layer_summary", "LAYER", "LAYER_STATS", "UNASSIGNED", "MASKED", "UNKNOWN"),
     **_names("subtract", "subtract_background", "upsample_crop_subtract_background", "frame_motions", "foreground_objects", "foreground_mask"),
+    **_names("erase", "upsample_crop_remove_objects", "grow_mask"),    # (remove_objects: the callable tool module below)
     **_names("interp", "interpolate", "upsample_crop_interpolate"),
     **_names("pipeline", "FlowPipeline"),
     **_names("node", "FlowNode"),
 }
 
 # the command-line modules that are returned as modules: each is callable as the function of its name in flowonthego_amd.flowfilter /
-# blockmotion / motion / objects / tracks / histograms / motionblur / plate / layers / subtract
-CLI_MODULES = ["filter_flow", "block_motion", "fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms", "motion_blur", "background", "motion_layers", "foreground"]
+# blockmotion / motion / objects / tracks / histograms / motionblur / plate / layers / subtract / erase
+CLI_MODULES = ["filter_flow", "block_motion", "fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms", "motion_blur", "background", "motion_layers", "foreground", "remove_objects"]
 
 
 def __getattr__(name):

@@ -413,6 +413,21 @@ class OFClass:
         return ofc_foreground(self, frames, ref=ref, model=model, low=low, high=high, window=window, min_area=min_area,
                               max_objects=max_objects, mode=mode, exclude_moving=exclude_moving)
 
+    def upsample_crop_remove_objects(self, flows, frames, plate, remove, index=None, origin=(0, 0), plate_code=None, mask=None, grow=2,
+                                     feather=3, dst=True, code=False, alpha=False, stats=False, fused=True):
+        """the frames with `remove`, grown and feathered, filled from the plate sampled along upsample_crop(flows), flows
+        (n, h_l, w_l, 2) of the pairs (frame, reference); fused: the full-resolution flows are never written -- flowonthego_amd.erase"""
+        from .erase import upsample_crop_remove_objects
+        return upsample_crop_remove_objects(self, flows, frames, plate, remove, index=index, origin=origin, plate_code=plate_code, mask=mask,
+                                            grow=grow, feather=feather, dst=dst, code=code, alpha=alpha, stats=stats, fused=fused)
+
+    def remove_objects(self, frames, ref=0, model="affine", low=8.0, high=24.0, window=1, min_area=64, max_objects=256, grow=2, feather=3):
+        """frames (T+1, ...) -> (clean, code, mask, plate): OFClass.foreground, then the confirmed objects, grown by `grow` pixels and
+        feathered over `feather` more, filled from the plate -- flowonthego_amd.erase"""
+        from .erase import ofc_remove_objects
+        return ofc_remove_objects(self, frames, ref=ref, model=model, low=low, high=high, window=window, min_area=min_area,
+                                  max_objects=max_objects, grow=grow, feather=feather)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

@@ -208,14 +208,21 @@ def ofc_foreground(ofc, frames, ref=0, model="affine", low=8.0, high=24.0, windo
     OFClass.background on the frame grid (plate, its code, and the motions reference -> frame it used), frame_motions,
     subtract_background(frames, plate, motions=..., plate_code=the plate's code, ...) over all T + 1 frames with code and evidence,
     foreground_objects and foreground_mask.  mask uint8 (T+1, h, w): the pixels of the confirmed objects."""
+    return _ofc_foreground(ofc, frames, ref, model, low, high, window, min_area, max_objects, mode, exclude_moving)[:5]
+
+
+def _ofc_foreground(ofc, frames, ref, model, low, high, window, min_area, max_objects, mode, exclude_moving):
+    """ofc_foreground's five results, then the plate's code and the motions frame -> reference it subtracted along (what
+    flowonthego_amd.erase goes on with)"""
     from .plate import _ofc_plate
     _plain(low, high, window, (0, 0), (True,))
     plate, pcode, _, motions = _ofc_plate(ofc, frames, ref=ref, model=model, mosaic=False, mode=mode, exclude_moving=exclude_moving,
                                           min_count=1)
-    code, evidence = subtract_background(frames, plate, motions=frame_motions(motions), plate_code=pcode, low=low, high=high, window=window,
-                                         code=True, evidence=True)
+    back = frame_motions(motions)
+    code, evidence = subtract_background(frames, plate, motions=back, plate_code=pcode, low=low, high=high, window=window, code=True,
+                                         evidence=True)
     objects, ids, confirmed = foreground_objects(code, evidence, 8, min_area, max_objects)
-    return foreground_mask(ids, confirmed), objects, confirmed, plate, code
+    return foreground_mask(ids, confirmed), objects, confirmed, plate, code, pcode, back
 
 
 callable_module(__name__, __name__, "subtract_background")

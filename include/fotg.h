@@ -1016,6 +1016,67 @@ int fotg_upsample_crop_subtract_u8(fotg_ctx *ctx, int n, const float *coarse_flo
                                    const unsigned char *plate_code, const unsigned char *mask, float low, float high, int window,
                                    unsigned char *code, short *diff, float *evidence, long long *stats, void *stream);
 
+/* ---- object removal: a mask grown by a disc, feathered at its rim and filled from the plate, csrc/erase.hip.h -------------------
+ * What background subtraction found (fotg_subtract, fotg_label_components), or any other mask, taken out of the frames: under the
+ * grown mask the frame is replaced by the plate sampled into the frame's own grid, with a ramp at the rim.
+ *
+ * n frames of w x h with 1 or 3 interleaved channels, f32 or 8-bit; P plates on a W x H canvas with integer origin (ox, oy), index,
+ * plate_code, mask and the three sources of the vector frame i -> reference (dense flows, six f64 parameters per frame through
+ * MotionSrc, a context's coarse flows through UpsampleSrc) exactly as in fotg_subtract.  remove: n x h x w bytes, non-zero = take
+ * this pixel out.  grow = G and feather = F are integers, 0 <= G <= 8, 0 <= F <= 8; R = G + F.  Per frame pixel (x, y), in this order:
+ *   1. Distance (integers).  D2 = the smallest (x - x')^2 + (y - y')^2 over the pixels (x', y') of the frame with remove != 0,
+ *      |x - x'| <= R and |y - y'| <= R; without one the pixel is far.  Pixels outside the frame hold nothing.
+ *   2. Weight, alpha in 0 .. 256 (integers).  far: alpha = 0;  D2 <= G * G: alpha = 256;  otherwise with F == 0: alpha = 0;  otherwise
+ *        D16 = floor(sqrt(256 * D2)), the exact integer root;  E = 16 * (G + F) - D16;
+ *        alpha = E <= 0 ? 0 : min(256, (256 * E + 8 * F) / (16 * F))          (integer division)
+ *      256 at distance G, 0 from distance G + F on, 16 steps per pixel between.
+ *   3. Sample, only where alpha > 0: steps 1 to 4 of fotg_subtract with the same helpers (warp_inside, warp_sat, clampi, warp_taps),
+ *      except that a NaN in the frame pixel does not disqualify:
+ *        (u, v) not finite, or mask[i][y][x] != 0:                                                            code 3
+ *        Xc = (float)(x + ox) + u;  Yc = (float)(y + oy) + v;  !warp_inside(Xc, Yc, W, H):                    code 2
+ *        plate_code[index[i]] non-zero at any of the four clamped tap pixels of fotg_warp at (Xc, Yc):        code 2
+ *        s = warp_taps(plate[index[i]], W, H, Xc, Yc);  any channel of s is NaN:                              code 3
+ *   4. Value, f the frame's pixel.  alpha == 0, or code 2 or 3: dst = f, copied bit for bit.  alpha == 256 and a good sample: dst = s
+ *      (8-bit: warp_to_u8(s)), code 1.  0 < alpha < 256 and a good sample: code 4, a = (float)alpha * 0.00390625f and per channel
+ *      dst = f + (s - f) * a, every operation rounded on its own (8-bit: through warp_to_u8).
+ *      alphabet: 0 untouched, 1 replaced, 2 no plate there (kept), 3 unknown (kept), 4 blended
+ *   5. Outputs, each optional, at least one: dst (the frames' type and shape), code (n x h x w uint8), alpha (n x h x w int16),
+ *      stats (n x 8 int64 per frame: [0..4] the pixels of code 0 .. 4, [5] the pixels with alpha == 256 and code 2 or 3 -- the holes,
+ *      where an object is still visible --, [6] the pixels with remove != 0, [7] the sum of alpha).  stats is cleared by a
+ *      stream-ordered memset inside the call and accumulated by integer atomics: the same bytes every run.
+ *   With alpha as the only output nothing is sampled: frames, the plate and the source of the vectors are not read and may be null;
+ *   alpha == 256 is then the dilation of remove by the disc of radius G (flowonthego_amd.erase.grow_mask).
+ *
+ * Everything is enqueued on `stream`; index is validated on the host and consumed before the call returns.
+ * FOTG_ERR_ARG, decided before the device is touched: n or P outside 1..65535, a frame or canvas side outside 1..16384, an origin
+ * beyond 2^20, channels not 1 or 3, grow or feather outside 0..8, a plate index outside 0 .. P-1 (a NULL index with P other than 1
+ * and n), a null remove, all four outputs null, a null frames, plate or source unless alpha is the only output, and by both rules
+ * of csrc/spans.h: an output (dst, code, alpha, stats) overlapping an input (frames, plate, the source, plate_code, mask, remove)
+ * -- overlap_any -- or another output -- overlap_among.  The fused forms also for a null or depth-mode context and n > max_batch. */
+int fotg_erase(int device, int n, const float *frames, int w, int h, int channels, int P, const float *plate, int W, int H, int ox, int oy,
+               const int *index, const float *flows, const unsigned char *plate_code, const unsigned char *mask, const unsigned char *remove,
+               int grow, int feather, float *dst, unsigned char *code, short *alpha, long long *stats, void *stream);
+int fotg_erase_u8(int device, int n, const unsigned char *frames, int w, int h, int channels, int P, const unsigned char *plate, int W, int H,
+                  int ox, int oy, const int *index, const float *flows, const unsigned char *plate_code, const unsigned char *mask,
+                  const unsigned char *remove, int grow, int feather, unsigned char *dst, unsigned char *code, short *alpha, long long *stats,
+                  void *stream);
+int fotg_erase_motion(int device, int n, const float *frames, int w, int h, int channels, int P, const float *plate, int W, int H, int ox,
+                      int oy, const int *index, const double *params, const unsigned char *plate_code, const unsigned char *mask,
+                      const unsigned char *remove, int grow, int feather, float *dst, unsigned char *code, short *alpha, long long *stats,
+                      void *stream);
+int fotg_erase_motion_u8(int device, int n, const unsigned char *frames, int w, int h, int channels, int P, const unsigned char *plate, int W,
+                         int H, int ox, int oy, const int *index, const double *params, const unsigned char *plate_code,
+                         const unsigned char *mask, const unsigned char *remove, int grow, int feather, unsigned char *dst,
+                         unsigned char *code, short *alpha, long long *stats, void *stream);
+int fotg_upsample_crop_erase(fotg_ctx *ctx, int n, const float *coarse_flows, const float *frames, int channels, int P, const float *plate,
+                             int W, int H, int ox, int oy, const int *index, const unsigned char *plate_code, const unsigned char *mask,
+                             const unsigned char *remove, int grow, int feather, float *dst, unsigned char *code, short *alpha,
+                             long long *stats, void *stream);
+int fotg_upsample_crop_erase_u8(fotg_ctx *ctx, int n, const float *coarse_flows, const unsigned char *frames, int channels, int P,
+                                const unsigned char *plate, int W, int H, int ox, int oy, const int *index, const unsigned char *plate_code,
+                                const unsigned char *mask, const unsigned char *remove, int grow, int feather, unsigned char *dst,
+                                unsigned char *code, short *alpha, long long *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
