@@ -33,14 +33,15 @@ LAZY = {
     **_names("layers", "upsample_crop_motion_layers", "layer_summary", "LAYER", "LAYER_STATS", "UNASSIGNED", "MASKED", "UNKNOWN"),
     **_names("subtract", "subtract_background", "upsample_crop_subtract_background", "frame_motions", "foreground_objects", "foreground_mask"),
     **_names("erase", "upsample_crop_remove_objects", "grow_mask"),    # (remove_objects: the callable tool module below)
+    **_names("morph", "morphology"),                                   # (clean_mask: the callable tool module below)
     **_names("interp", "interpolate", "upsample_crop_interpolate"),
     **_names("pipeline", "FlowPipeline"),
     **_names("node", "FlowNode"),
 }
 
 # the command-line modules that are returned as modules: each is callable as the function of its name in flowonthego_amd.flowfilter /
-# blockmotion / motion / objects / tracks / histograms / motionblur / plate / layers / subtract / erase
-CLI_MODULES = ["filter_flow", "block_motion", "fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms", "motion_blur", "background", "motion_layers", "foreground", "remove_objects"]
+# blockmotion / motion / objects / tracks / histograms / motionblur / plate / layers / subtract / erase / morph
+CLI_MODULES = ["filter_flow", "block_motion", "fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms", "motion_blur", "background", "motion_layers", "foreground", "remove_objects", "clean_mask"]
 
 
 def __getattr__(name):

@@ -142,19 +142,22 @@ def grow_mask(remove, grow):
 
 
 def ofc_remove_objects(ofc, frames, ref=0, model="affine", low=8.0, high=24.0, window=1, min_area=64, max_objects=256, grow=2, feather=3,
-                       mask=None):
+                       mask=None, open=0, close=0):
     """OFClass.remove_objects: frames (T+1, h, w[, c]) -> (clean, code, mask, plate).  The composition, call for call:
     OFClass.foreground(frames, ref, model, low, high, window, min_area, max_objects) for the mask of the confirmed objects and the
     plate, then remove_objects(frames, plate, mask, motions=frame_motions(the plate's motions), plate_code=the plate's code, grow=,
     feather=, dst=True, code=True) -- the code OFClass.background returns with this plate and the motions frame -> reference
     OFClass.foreground subtracted along; neither is computed again.  clean: the frames without the confirmed objects; code:
     remove_objects' code map (CODES).
+    open, close: OFClass.foreground's, the radii the foreground is opened and closed by before the objects are taken (OFClass.remove_objects
+    keeps its signature: the cleaning reaches the removal through this function and the tool's --open and --close).
     mask (the tool's --mask): a uint8 map (T+1, h, w) to take out instead; then nothing is subtracted: OFClass.background's plate,
     code and motions, and remove_objects with them."""
     _plain(grow, feather, (0, 0), (True,))
     if mask is None:
         from .subtract import _ofc_foreground
-        mask, _, _, plate, _, pcode, back = _ofc_foreground(ofc, frames, ref, model, low, high, window, min_area, max_objects, "median", True)
+        mask, _, _, plate, _, pcode, back = _ofc_foreground(ofc, frames, ref, model, low, high, window, min_area, max_objects, "median", True,
+                                                             open, close)
     else:
         from .plate import _ofc_plate
         from .subtract import frame_motions

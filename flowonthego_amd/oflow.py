@@ -406,12 +406,13 @@ class OFClass:
                                                  fused=fused)
 
     def foreground(self, frames, ref=0, model="affine", low=8.0, high=24.0, window=1, min_area=64, max_objects=256, mode="median",
-                   exclude_moving=True):
+                   exclude_moving=True, open=0, close=0):
         """frames (T+1, ...) -> (mask, objects, confirmed, plate, code): the plate of the shot on frame ref's grid, every frame
-        subtracted from it, and the components that hold a strong pixel -- flowonthego_amd.subtract"""
+        subtracted from it, and the components that hold a strong pixel; open, close: the radii 0 .. 8 the foreground is opened and
+        closed by before the components are taken (0, 0: as it is) -- flowonthego_amd.subtract, flowonthego_amd.morph"""
         from .subtract import ofc_foreground
         return ofc_foreground(self, frames, ref=ref, model=model, low=low, high=high, window=window, min_area=min_area,
-                              max_objects=max_objects, mode=mode, exclude_moving=exclude_moving)
+                              max_objects=max_objects, mode=mode, exclude_moving=exclude_moving, open=open, close=close)
 
     def upsample_crop_remove_objects(self, flows, frames, plate, remove, index=None, origin=(0, 0), plate_code=None, mask=None, grow=2,
                                      feather=3, dst=True, code=False, alpha=False, stats=False, fused=True):

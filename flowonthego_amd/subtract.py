@@ -177,11 +177,20 @@ def frame_motions(motions):
     return torch.stack((i[0] - 1.0, i[1], i[2], i[3], i[4] - 1.0, i[5]), dim=1).contiguous()
 
 
-def foreground_objects(code, evidence, connectivity=8, min_area=64, max_objects=256):
+def foreground_objects(code, evidence, connectivity=8, min_area=64, max_objects=256, open=0, close=0):
     """code and evidence of subtract_background -> (objects, ids, confirmed): label_components(code, fg=(1, 4), values=evidence,
     ids=True) and confirmed = objects[..., 9] > 0, a bool per row.  sum_u / 256 of a row is the number of strong (code 4) pixels
-    of the component, so a component of weak pixels is confirmed only if it holds a strong one: the hysteresis."""
+    of the component, so a component of weak pixels is confirmed only if it holds a strong one: the hysteresis.
+    open > 0 or close > 0 (each 0 .. 8): the set fg = (1, 4) of the code map is cleaned first, cleaned = morph.clean_mask(code, open,
+    close, fg=(1, 4)), and the components are those of the cleaned map: label_components(cleaned, fg=(1,), values=evidence, ids=True).
+    confirmed keeps its meaning: a pixel the closing adds has evidence 0, a strong pixel the opening deletes belongs to no component."""
     from .objects import label_components
+    if open or close:
+        from .morph import clean_mask
+        cleaned = clean_mask(code, open=open, close=close, fg=FG)
+        objects, ids = label_components(cleaned, fg=(1,), connectivity=connectivity, values=evidence, min_area=min_area, max_objects=max_objects,
+                                        ids=True)
+        return objects, ids, objects[..., 9] > 0
     objects, ids = label_components(code, fg=FG, connectivity=connectivity, values=evidence, min_area=min_area, max_objects=max_objects,
                                     ids=True)
     return objects, ids, objects[..., 9] > 0
@@ -203,25 +212,30 @@ def foreground_mask(ids, confirmed):
 
 
 def ofc_foreground(ofc, frames, ref=0, model="affine", low=8.0, high=24.0, window=1, min_area=64, max_objects=256, mode="median",
-                   exclude_moving=True):
+                   exclude_moving=True, open=0, close=0):
     """OFClass.foreground: frames (T+1, h, w[, c]) -> (mask, objects, confirmed, plate, code).  The composition, call for call:
     OFClass.background on the frame grid (plate, its code, and the motions reference -> frame it used), frame_motions,
     subtract_background(frames, plate, motions=..., plate_code=the plate's code, ...) over all T + 1 frames with code and evidence,
-    foreground_objects and foreground_mask.  mask uint8 (T+1, h, w): the pixels of the confirmed objects."""
-    return _ofc_foreground(ofc, frames, ref, model, low, high, window, min_area, max_objects, mode, exclude_moving)[:5]
+    foreground_objects(code, evidence, 8, min_area, max_objects, open, close) -- with open or close above 0 on the code map cleaned
+    by morph.clean_mask -- and foreground_mask.  mask uint8 (T+1, h, w): the pixels of the confirmed objects."""
+    return _ofc_foreground(ofc, frames, ref, model, low, high, window, min_area, max_objects, mode, exclude_moving, open, close)[:5]
 
 
-def _ofc_foreground(ofc, frames, ref, model, low, high, window, min_area, max_objects, mode, exclude_moving):
+def _ofc_foreground(ofc, frames, ref, model, low, high, window, min_area, max_objects, mode, exclude_moving, open=0, close=0):
     """ofc_foreground's five results, then the plate's code and the motions frame -> reference it subtracted along (what
     flowonthego_amd.erase goes on with)"""
     from .plate import _ofc_plate
     _plain(low, high, window, (0, 0), (True,))
+    if open or close:
+        from .morph import _radius
+        _radius(open, "open")
+        _radius(close, "close")
     plate, pcode, _, motions = _ofc_plate(ofc, frames, ref=ref, model=model, mosaic=False, mode=mode, exclude_moving=exclude_moving,
                                           min_count=1)
     back = frame_motions(motions)
     code, evidence = subtract_background(frames, plate, motions=back, plate_code=pcode, low=low, high=high, window=window, code=True,
                                          evidence=True)
-    objects, ids, confirmed = foreground_objects(code, evidence, 8, min_area, max_objects)
+    objects, ids, confirmed = foreground_objects(code, evidence, 8, min_area, max_objects, open, close)
     return foreground_mask(ids, confirmed), objects, confirmed, plate, code, pcode, back
 
 

@@ -1077,6 +1077,33 @@ int fotg_upsample_crop_erase_u8(fotg_ctx *ctx, int n, const float *coarse_flows,
                                 const unsigned char *mask, const unsigned char *remove, int grow, int feather, unsigned char *dst,
                                 unsigned char *code, short *alpha, long long *stats, void *stream);
 
+/* ---- binary morphology of masks and code maps: erode, dilate, open and close by a disc, csrc/morph.hip.h ----------------------
+ * The step between a code map (fotg_subtract, fotg_fit_motion, fotg_fb_check) and what reads masks (fotg_label_components,
+ * fotg_erase, fotg_plate's exclude): speckle is opened away, pin-holes are closed.  Exact and in integers.
+ *
+ * n maps of w x h bytes, 1 <= w, h <= 16384, n <= 65535.  A pixel is set if its byte belongs to the foreground set: with
+ * fg_codes == 0 every non-zero byte; otherwise fg_codes is an 8-bit set as in fotg_label_components and byte b is set iff
+ * b < 8 && ((fg_codes >> b) & 1), so that a code map goes in unconverted.  The structuring element is the disc
+ * dx^2 + dy^2 <= r^2 with r an integer in 0 .. 8, the disc of fotg_erase's grow.  Per map X and stage, on the whole frame:
+ *   dilate(X, r): a pixel is set iff some pixel of the frame within the disc around it is set;
+ *   erode(X, r):  a pixel is set iff every pixel of the frame within the disc around it is set.
+ * Pixels outside the frame take no part in either: the frame border does not erode, and inside the frame exactly
+ * erode(X, r) = not dilate(not X, r).  r = 0 is the identity and yields the 0 / 1 map of the foreground set.
+ * A call evaluates a chain of nstage = 1 or 2 stages, stage k an erode (ops[k] == 0) or a dilate (ops[k] == 1) with its own radius
+ * radii[k], the second on the whole-frame result of the first:
+ *   open(X, r) = dilate(erode(X, r), r);  close(X, r) = erode(dilate(X, r), r).
+ * Outputs, each optional, at least one: out (n x h x w uint8, 0 or 1), stats (n x 4 int64 per map: [0] the set pixels of the
+ * input, [1] the set pixels of the result, [2] the pixels added -- set in the result and not in the input --, [3] the pixels
+ * removed).  stats is cleared by a stream-ordered memset inside the call and accumulated by integer atomics: the same bytes every run.
+ *
+ * One launch per call, whatever the chain: the intermediate map of an opening or a closing never reaches memory.  Everything is
+ * enqueued on `stream`; ops and radii are HOST arrays of nstage ints, consumed before the call returns; nothing synchronises.
+ * FOTG_ERR_ARG, decided before the device is touched: n outside 1..65535, w or h outside 1..16384, a null src, fg_codes outside
+ * 0..255, nstage not 1 or 2, null ops or radii, an op other than 0 (erode) and 1 (dilate), a radius outside 0..8, both outputs null,
+ * and by both rules of csrc/spans.h: out or stats overlapping src -- overlap_any -- or each other -- overlap_among. */
+int fotg_morph(int device, int n, const unsigned char *src, int w, int h, int fg_codes, int nstage, const int *ops, const int *radii,
+               unsigned char *out, long long *stats, void *stream);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
