@@ -34,14 +34,15 @@ LAZY = {
     **_names("subtract", "subtract_background", "upsample_crop_subtract_background", "frame_motions", "foreground_objects", "foreground_mask"),
     **_names("erase", "upsample_crop_remove_objects", "grow_mask"),    # (remove_objects: the callable tool module below)
     **_names("morph", "morphology"),                                   # (clean_mask: the callable tool module below)
+    **_names("fill", "fill_flow", "fill_removed", "upsample_crop_fill_flow", "FILL_CODES", "FILL_STATS"),      # (fill_holes: the callable tool module below)
     **_names("interp", "interpolate", "upsample_crop_interpolate"),
     **_names("pipeline", "FlowPipeline"),
     **_names("node", "FlowNode"),
 }
 
 # the command-line modules that are returned as modules: each is callable as the function of its name in flowonthego_amd.flowfilter /
-# blockmotion / motion / objects / tracks / histograms / motionblur / plate / layers / subtract / erase / morph
-CLI_MODULES = ["filter_flow", "block_motion", "fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms", "motion_blur", "background", "motion_layers", "foreground", "remove_objects", "clean_mask"]
+# blockmotion / motion / objects / tracks / histograms / motionblur / plate / layers / subtract / erase / morph / fill
+CLI_MODULES = ["filter_flow", "block_motion", "fit_motion", "stabilize", "moving_objects", "track_objects", "motion_histograms", "motion_blur", "background", "motion_layers", "foreground", "remove_objects", "clean_mask", "fill_holes"]
 
 
 def __getattr__(name):

@@ -132,6 +132,9 @@ SYMBOLS = [
     ("fotg_upsample_crop_erase", C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp] * 4 + [C.c_int, C.c_int] + [vp] * 5),
     ("fotg_upsample_crop_erase_u8", C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp] + [C.c_int] * 4 + [vp] * 4 + [C.c_int, C.c_int] + [vp] * 5),
     ("fotg_morph", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, vp]),
+    ("fotg_fill", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
+    ("fotg_fill_u8", C.c_int, [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
+    ("fotg_fill_scratch", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
     ("fotg_level_size", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_out_size", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fotg_num_patches", C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -3,7 +3,8 @@ into the frame's own grid along the frame's motion, with the sampling rules of t
 fotg_erase_motion / fotg_upsample_crop_erase of libfotg.so.  The definition, in integers and f32 and in order, is in include/fotg.h
 and csrc/erase.hip.h.  One kernel stages the mask of a tile and its halo on chip as bits, takes the capped distance to it in two
 passes and writes every output once; a tile with nothing to remove is copied.  It runs in HIP only, there is no CPU fallback.
-Where the plate knows nothing the frame is kept and the pixel is counted as a hole: nothing is inpainted.
+Where the plate knows nothing the frame is kept and the pixel is counted as a hole: nothing is inpainted here;
+flowonthego_amd.fill.fill_removed fills exactly those pixels from the frame around them.
 
 The module is callable: flowonthego_amd.erase(frames, plate, remove, ...) is flowonthego_amd.erase.remove_objects(frames, plate, remove, ...)."""
 import torch

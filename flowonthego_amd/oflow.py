@@ -429,6 +429,23 @@ class OFClass:
         return ofc_remove_objects(self, frames, ref=ref, model=model, low=low, high=high, window=window, min_area=min_area,
                                   max_objects=max_objects, grow=grow, feather=feather)
 
+    def remove_objects_filled(self, frames, **kw):
+        """OFClass.remove_objects(frames, **kw), then the holes it leaves where the plate knows nothing filled from the frame around
+        them by pull-push: (clean, code, mask, plate, fill_code) -- flowonthego_amd.fill"""
+        from .fill import ofc_remove_objects_filled
+        return ofc_remove_objects_filled(self, frames, **kw)
+
+    def upsample_crop_fill_flow(self, flow, mask=None):
+        """upsample_crop(flow) with the vectors under mask (and the unknown ones) filled from the others -- flowonthego_amd.fill"""
+        from .fill import upsample_crop_fill_flow
+        return upsample_crop_fill_flow(self, flow, mask)
+
+    def calc_filled(self, I0, I1, both=False, code=False, stats=False):
+        """the full-resolution flow of n pairs with the vectors the forward-backward check rejects filled from the consistent ones by
+        pull-push (a bidir context); both=True also returns the backward flow filled -- flowonthego_amd.fill"""
+        from .fill import ofc_calc_filled
+        return ofc_calc_filled(self, I0, I1, both=both, code=code, stats=stats)
+
     def bidirectional_flows(self, I0, I1):
         """the coarse (fw, bw) of n pairs for a post-pass that also needs the frames (upsample_crop_fb_check, upsample_crop_warp,
         upsample_crop_interpolate): calc_bidirectional or its 8-bit form, by the frames' dtype"""

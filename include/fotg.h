@@ -1104,6 +1104,51 @@ int fotg_upsample_crop_erase_u8(fotg_ctx *ctx, int n, const float *coarse_flows,
 int fotg_morph(int device, int n, const unsigned char *src, int w, int h, int fg_codes, int nstage, const int *ops, const int *radii,
                unsigned char *out, long long *stats, void *stream);
 
+/* ---- hole filling by pull-push: frames and flows inpainted from their known pixels, csrc/fill.hip.h --------------------------------
+ * What fotg_erase leaves as holes (no plate), what fotg_fb_check marks and fotg_flow_filter cannot reach, the unknown vectors of a
+ * .flo file and a sparse set of vectors all become a dense image: a pyramid of sums over the known pixels (pull) is interpolated back
+ * down into the holes (push).  Gortler et al., "The Lumigraph", 1996; Kraus, "The pull-push algorithm revisited", 2009.
+ *
+ * n images of w x h pixels with ch interleaved channels, 1 <= w, h <= 16384, 1 <= n <= 65535.  f32 images take ch in {1, 2, 3}, uint8
+ * images ch in {1, 3}.  hole is n x h x w uint8, or NULL (f32 only).  fg_codes in 0 .. 255 follows fotg_morph's rule: with
+ * fg_codes == 0 every non-zero byte is a hole; otherwise byte b is a hole iff b < 8 && ((fg_codes >> b) & 1), so that a code map
+ * goes in unconverted.
+ * Known pixels: a pixel is known iff it is not a hole and, for f32, every channel v is finite with |v| <= 32768.  A NaN, an infinity
+ * and the .flo unknown marker 1e9 are therefore holes with no map at all.
+ * Pull (exact integers): q = lrintf(256 v) per channel (256 v is exact in f32; for uint8 q = 256 v).  Level 0 has S_0 = q and N_0 = 1
+ * at known pixels and 0 elsewhere.  Level l+1 has size w_{l+1} = (w_l + 1) >> 1, h_{l+1} = (h_l + 1) >> 1; S_{l+1}(X, Y) and
+ * N_{l+1}(X, Y) are the sums over the children (2X + i, 2Y + j), i, j in {0, 1}, that lie inside level l.  L is the first level of
+ * size 1 x 1.  S is an int64 per channel with |S| <= 2^51, N an integer <= 2^28.
+ * Empty image: if N_L == 0 the image knows nothing; then dst = src bit for bit and code is 2 at every hole pixel and 0 at every known
+ * pixel.
+ * Mean of a block with N_l > 0: M_l = (float)((double)S_l / (double)(256 N_l)), one f64 division rounded once to f32 (exact to
+ * restate, because |S| < 2^53).
+ * Push, for l = L-1 down to 0: F_L = M_L.  At level l a pixel with N_l > 0 and l >= 1 has F_l = M_l.  A pixel with N_l == 0 at (x, y)
+ * takes the bilinear value of its four parents: px = x >> 1, px2 = clamp(px + (x & 1 ? 1 : -1), 0, w_{l+1} - 1), py and py2 likewise;
+ * a = F_{l+1}(px, py), b = F_{l+1}(px2, py), c = F_{l+1}(px, py2), d = F_{l+1}(px2, py2);
+ *   F_l = ((a*9 + b*3) + (c*3 + d)) * 0.0625 in f32, in exactly this order, with no contraction.
+ * At level 0 a known pixel keeps its source value bit for bit (it does not become its quantised value); a hole pixel gets F_0, for
+ * uint8 rintf, clamped to [0, 255] (fotg_warp's to_u8).
+ * Outputs, each optional, at least one: dst (same type and shape as src), code (n x h x w uint8: 0 known (kept), 1 filled, 2 nothing
+ * known in this image (kept)), stats (n x 4 int64: known, filled, unfilled, depth).  depth = 1 + the largest l at which some block
+ * has N_l == 0, and 0 without holes: the log2 scale of the widest hole.  stats is zeroed by a stream-ordered memset and accumulated
+ * with integer atomics and integer maxima: the same bytes every run.
+ *
+ * Three launches per chunk of images (pull, top, push) over stream-ordered memory of the call: fotg_fill_scratch states its size,
+ * host only, the device is not touched.  A batch whose levels would take more than 1 GiB is worked through in chunks of as many
+ * images as fit in 1 GiB (at least one) inside the call, so a call takes at most max(the bytes of one image's levels, 1 GiB); one
+ * image takes about 0.35 of its f32 size.  Everything is enqueued on `stream`; nothing synchronises.  Not built: filling in place,
+ * an edge-aware or guided push, weights other than 0 / 1, inpainting from other frames, more than 3 channels.
+ * FOTG_ERR_ARG, decided before the device is touched: n outside 1..65535, w or h outside 1..16384, ch outside {1, 2, 3} (f32) or
+ * {1, 3} (uint8), fg_codes outside 0..255, a null src, a null hole with uint8, all three outputs null, and by both rules of
+ * csrc/spans.h: an output overlapping src or hole -- overlap_any -- or another output -- overlap_among.  fotg_fill_scratch: the same
+ * ranges, and a null bytes. */
+int fotg_fill(int device, int n, const float *src, int w, int h, int ch, const unsigned char *hole, int fg_codes, float *dst,
+              unsigned char *code, long long *stats, void *stream);
+int fotg_fill_u8(int device, int n, const unsigned char *src, int w, int h, int ch, const unsigned char *hole, int fg_codes,
+                 unsigned char *dst, unsigned char *code, long long *stats, void *stream);
+int fotg_fill_scratch(int n, int w, int h, int ch, long long *bytes);
+
 /* op.verbosity of the reference (src/oflow.cpp:246-365, kroeger/oflow.cpp:298-360).  0 (default): silent, asynchronous.
  * > 0: every flow call (fotg_calc, fotg_calc_batch, ...) waits for its launches and prints "TIME (O.Flow Run-Time   ) (ms): ..."
  * (the flow without the pyramid, like the reference); > 1: also one "TIME (Sc: .., #p: .., pconst, pinit, poptim, cflow, tvopt,
