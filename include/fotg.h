@@ -274,6 +274,17 @@ int fotg_upsample_crop(fotg_ctx *ctx, int n, const float *flow, float *out, void
 int fotg_gradient_magnitude(int device, int n, const float *frames, int w_org, int h_org, int channels, int sc_f, float *out, void *stream);
 int fotg_gradient_magnitude_u8(int device, int n, const unsigned char *frames, int w_org, int h_org, int channels, int sc_f, float *out, void *stream);
 
+/* STREAM-ORDERED MEMORY.  The add-ons below that keep partial sums, planes or levels "in stream-ordered memory of the call" take it
+ * with hipMallocAsync and give it back with hipFreeAsync, both on `stream`; nothing else in them touches the host, and the first such
+ * call enqueued behind pending work on a stream returns at once.  A further call on the same stream may wait ON THE HOST until the
+ * stream has reached the earlier call's free: the runtime's hipMallocAsync blocks the calling thread when the block it would reuse was
+ * freed on that stream and the free has not executed yet (measured on the MI355X; no attribute of the device's pool changes it).
+ * Results and stream order are not affected.  Entry points: fotg_flow_color and fotg_upsample_crop_color without `stats` (the
+ * per-image keys are then the call's own), fotg_warp*, fotg_interp*, fotg_fit_motion, fotg_motion_layers,
+ * fotg_label_components, fotg_temporal_filter*, fotg_flow_filter*, fotg_block_motion, fotg_motion_blur, fotg_plate*, fotg_subtract*,
+ * fotg_erase*, fotg_fill* and their fotg_upsample_crop_* forms.  A caller that must not block keeps at most one such call pending
+ * per stream, or gives each its own stream. */
+
 /* Middlebury colour code of a flow (flow_code/C/color_flow.cpp MotionToColor + colorcode.cpp computeColor).
  * flow: n x h x w x 2 f32 (device); rgb: n x h x w x 3 uint8 (device), R, G, B per pixel (the byte order of the reference's PNG).
  * Normalised PER IMAGE by maxrad = the largest |(u, v)| over its known vectors, or by maxmotion when maxmotion > 0 (a maxrad of 0

@@ -3,6 +3,8 @@
 // among the vectors the flow proposes for the block by the SAD of its prediction from ref, optionally refined by full-, half- and
 // quarter-pel steps.  All pointers are device pointers.  Asynchronous on `stream` (a hipStream_t, 0 = the null stream); each call
 // returns a FOTG_* status.  The definition, all of it integer arithmetic, is in include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_BLOCKMOTION_HEADER
 #define FOTG_BLOCKMOTION_HEADER
 #include "../fotg.h"

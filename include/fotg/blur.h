@@ -2,6 +2,8 @@
 // a shutter simulated per frame by the tile-max / neighbour-max reconstruction filter, for float32 and 8-bit frames of 1 or 3
 // channels.  Device pointers throughout, asynchronous on `stream` (a hipStream_t, 0 = the null stream); every call returns a
 // FOTG_* status.  The definition is in include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_BLUR_HEADER
 #define FOTG_BLUR_HEADER
 #include "../fotg.h"

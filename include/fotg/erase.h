@@ -3,6 +3,8 @@
 // frames, plate, the source of the vectors, plate_code, mask, remove and the outputs are device pointers; index is a HOST array,
 // consumed before the call returns.  Asynchronous on `stream` (a hipStream_t, 0 = the null stream); each call returns a FOTG_*
 // status.  The definition is in include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_ERASE_HEADER
 #define FOTG_ERASE_HEADER
 #include "../fotg.h"

@@ -2,6 +2,8 @@
 // unknown pixels of frames and flows filled from the known ones, at any hole size.  src, hole and the outputs are device pointers.
 // Asynchronous on `stream` (a hipStream_t, 0 = the null stream); each call returns a FOTG_* status.  The definition is in
 // include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_FILL_HEADER
 #define FOTG_FILL_HEADER
 #include "../fotg.h"

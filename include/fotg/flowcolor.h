@@ -4,6 +4,8 @@
 //   OFC::ReadFlowFile    flowIO.cpp ReadFlowFile: a Middlebury .flo into a host vector (h x w x 2 float32)
 //   OFC::SavePNG         a dependency-free 8-bit RGB PNG writer (stored deflate blocks, CRC-32, Adler-32): no libpng, no zlib
 // Plain C++ (no HIP header needed): the device pointers are the caller's.
+// Stream-ordered memory (a call without `stats` keeps its per-image keys there): a second call on a stream whose earlier call is
+// still pending may wait on the host (include/fotg.h, STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_OFC_FLOWCOLOR_HEADER
 #define FOTG_OFC_FLOWCOLOR_HEADER
 #include <cstdint>

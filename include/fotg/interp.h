@@ -3,6 +3,8 @@
 // photo-consistency, holes filled from the other direction, both frames sampled and blended with occlusion reasoning (Baker et
 // al., "A Database and Evaluation Methodology for Optical Flow", section 3.3).  Device pointers throughout, asynchronous on
 // `stream` (a hipStream_t, 0 = the null stream); each call returns a FOTG_* status.  The definition is in include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_INTERP_HEADER
 #define FOTG_INTERP_HEADER
 #include "../fotg.h"

@@ -2,6 +2,8 @@
 // eight motions of one model (translation, similarity, affine) fitted to one flow, a label per pixel (the layer; 253 unassigned,
 // 254 excluded by the mask, 255 unknown), a record per layer.  Device pointers throughout, asynchronous on `stream` (a hipStream_t,
 // 0 = the null stream); each call returns a FOTG_* status.  The definition is in include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_LAYERS_HEADER
 #define FOTG_LAYERS_HEADER
 #include "motion.h"

@@ -3,6 +3,8 @@
 // 1 moves on its own, 2 excluded by the mask, 3 unknown) and the motion as a flow for the warp.  Device pointers throughout,
 // asynchronous on `stream` (a hipStream_t, 0 = the null stream); each call returns a FOTG_* status.  The definition is in
 // include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_MOTION_HEADER
 #define FOTG_MOTION_HEADER
 #include "../fotg.h"

@@ -2,6 +2,8 @@
 // of chosen codes (for moving objects: code 1 of the motion fit) grouped into regions, a record of eleven 64-bit integers each.
 // Device pointers throughout, asynchronous on `stream` (a hipStream_t, 0 = the null stream); the call returns a FOTG_* status.  The
 // definition is in include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_OBJECTS_HEADER
 #define FOTG_OBJECTS_HEADER
 #include "../fotg.h"

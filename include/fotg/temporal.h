@@ -4,6 +4,8 @@
 // masks, ref and the outputs are device pointers; center, neighbors and gains are HOST arrays, consumed before the call returns.
 // Asynchronous on `stream` (a hipStream_t, 0 = the null stream); each call returns a FOTG_* status.  The definition is in
 // include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_TEMPORAL_HEADER
 #define FOTG_TEMPORAL_HEADER
 #include "../fotg.h"

@@ -2,6 +2,8 @@
 // 8-bit forms): the reference's image_warp with per-pixel codes (0 valid, 1 occluded, 2 the vector leaves the frame, 3 unknown:
 // the alphabet of include/fotg/fbcheck.h) and photometric residuals.  Device pointers throughout, asynchronous on `stream` (a
 // hipStream_t, 0 = the null stream); each call returns a FOTG_* status.  The definition is in include/fotg.h.
+// Stream-ordered memory: a second call on a stream whose earlier call is still pending may wait on the host (include/fotg.h,
+// STREAM-ORDERED MEMORY); the first returns at once.
 #ifndef FOTG_WARP_HEADER
 #define FOTG_WARP_HEADER
 #include "../fotg.h"
